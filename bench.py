@@ -1,8 +1,17 @@
 #!/usr/bin/env python3
 """Benchmark: decoded+triangulated camera px/s (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
+
+A plain run sets up the resident inputs, warms up, times the K steps, writes
+the last timed step's outputs if ``--dump-outputs DIR`` is given, and prints
+one JSON line with the headline figure.  ``--full`` adds every other leg to
+the run and to the line: the CPU baselines, the oracle check of the last
+timed step, the per-step event window, the distinct-views control window, the
+per-kernel and roofline passes, the cloud-only and other-xyz windows, the
+one-shot latencies and, with N > 1, the timed gather and the strong-scaled
+config-3 leg.
 
 A step is one pass of the hot path over one batch of synthetic views resident
 in HBM -- k_stats (black-plane histogram, max(white - black)), k_decode (Gray
@@ -22,7 +31,7 @@ default 300 ms of back-to-back steps, so the GPU's clocks and power state are
 at their steady state when the timed window opens -- a bench that follows an
 idle GPU would otherwise time the clock ramp), then, with no idle gap,
 exactly K steps between barrier + synchronize pairs (garbage collection off);
-then an identical window with one HIP event per step boundary on the stream
+then (``--full``) an identical window with one HIP event per step boundary on the stream
 (per-step min / median / max in "timing.step_us"; the events add idle time,
 so they stay out of the headline window).  Max over ranks.
 
@@ -33,7 +42,7 @@ view stays in the 256 MB Infinity Cache until its next step.
 Multi-GPU: weak scaling by default (views sharded over ranks with no
 data-path collective); the gather of the clouds to rank 0 (RCCL: torch's
 communicator, or ``--gather native`` = the library's own sl_gather) is timed
-separately and described in "multi_gpu".
+separately (``--full``) and described in "multi_gpu".
 """
 from __future__ import annotations
 
@@ -160,6 +169,17 @@ def parse(argv=None):
     ap.add_argument("--traffic", default=None,
                     help="PMC-derived HBM bytes per step (committed profile of the same workload, "
                          "scripts/traffic_from_pmc.py); default " + TRAFFIC_DIR + "/traffic_<config>.json")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline window, run every other leg of the bench: the CPU baselines, the "
+                         "oracle check of the last timed step (--verify), the per-step event window, the control "
+                         "window (--ring-control), the per-kernel and roofline passes, the cloud-only and other-xyz "
+                         "windows (--secondary), the one-shot latency block (--single-shot) and, N > 1, the timed "
+                         "gather and the strong-scaled leg (--strong-leg); each leg's own switch still applies.  "
+                         "Without it (default) the run sets up, warms up, times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="after the timed window, write what its last step returned (col_map, row_map, mask, xyz, "
+                         "bgr, view_offsets) as DIR/<name>.npy (float32; view_offsets float64); an array larger "
+                         "than 8 MB is written as a fixed, seeded sample of its elements (maps) or rows (cloud)")
     a = ap.parse_args(argv)
     if a.steps is None:
         a.steps = CONFIGS[a.config].get("steps", 20)
@@ -206,12 +226,14 @@ def my_views(scaling: str, V_cfg: int, world: int, rank: int) -> list[int]:
     return [rank * V_cfg + v for v in range(V_cfg)]
 
 
-def gather_report(el_s: float, n_local: int, bytes_per_point: int, device, gather_fn, distributed: bool):
+def gather_report(el_s: float, n_local: int, bytes_per_point: int, device, gather_fn, distributed: bool,
+                  timed_gather: bool = True):
     """Multi-rank facts of the timed run, identical on every rank, for rank 0's
     line: the communicator size torch.distributed sees, every rank's seconds
-    for the K steps and its point count; then one timed gather of the clouds
-    to rank 0 (gather_fn() -> counts as the gather's own communicator saw
-    them) with its bytes (the payload that crossed to rank 0) and GB/s."""
+    for the K steps and its point count; then (``timed_gather``) one timed
+    gather of the clouds to rank 0 (gather_fn() -> counts as the gather's own
+    communicator saw them) with its bytes (the payload that crossed to rank 0)
+    and GB/s."""
     world = dist.get_world_size() if distributed else 1
     t = torch.tensor([el_s, float(n_local)], dtype=torch.float64, device=device)
     if distributed:
@@ -222,7 +244,7 @@ def gather_report(el_s: float, n_local: int, bytes_per_point: int, device, gathe
     per_rank_s = [float(o[0].item()) for o in outs]
     per_rank_pts = [int(o[1].item()) for o in outs]
     rep = {"comm_size": world, "per_rank_s": per_rank_s, "per_rank_points": per_rank_pts}
-    if not distributed:
+    if not distributed or not timed_gather:
         return rep
     dist.barrier()
     if device.type == "cuda":
@@ -634,6 +656,52 @@ def cpu_baseline_single(a, cfg, cfg_idx, multi):
     return out
 
 
+DUMP_ARRAY_BYTES = 8 * 2 ** 20  # per written array (six at the most: under 64 MB in all)
+DUMP_SEED = 20240229
+
+
+def dump_sample(total, width):
+    """The sample ``--dump-outputs`` writes of an array of ``total`` elements
+    or rows of ``width`` float32 each: None (the whole array) up to
+    DUMP_ARRAY_BYTES, else sorted indices drawn from the size alone, so two
+    builds that return equally many points write the same rows."""
+    cap = DUMP_ARRAY_BYTES // (4 * width)
+    if total <= cap:
+        return None
+    return np.sort(np.random.default_rng([DUMP_SEED, total]).choice(total, cap, replace=False))
+
+
+def dump_outputs(path, res):
+    """``--dump-outputs``: what a step's call returned (``res``, the dict of
+    decode_triangulate) as ``path``/<name>.npy -- col_map, row_map and mask
+    ([V, H, W], when the config writes maps), xyz and bgr (the cloud's
+    view_offsets[-1] rows) as float32, view_offsets as float64; the three
+    maps at the same dump_sample elements, xyz and bgr at the same
+    dump_sample rows.  -> {name: {"shape": the written array's, "of": the
+    whole array's elements or rows}}"""
+    os.makedirs(path, exist_ok=True)
+    cloud = res["cloud"]
+    vo = cloud.view_offsets.cpu().numpy()
+    n = int(vo[-1])
+    arrays = {"view_offsets": (vo.astype(np.float64), vo.shape[0])}
+    if res.get("col_map") is not None:
+        total = res["col_map"].numel()
+        idx = dump_sample(total, 1)
+        for name, key in (("col_map", "col_map"), ("row_map", "row_map"), ("mask", "mask")):
+            t = res[key]
+            if idx is not None:
+                t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+            arrays[name] = (t.cpu().numpy().astype(np.float32), total)
+    rows = dump_sample(n, 3)
+    for name, t in (("xyz", cloud.xyz[:n]), ("bgr", cloud.bgr[:n])):
+        if rows is not None:
+            t = t[torch.from_numpy(rows).to(t.device)]
+        arrays[name] = (t.cpu().numpy().astype(np.float32), n)
+    for name, (arr, _) in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
+    return {name: {"shape": list(arr.shape), "of": int(of)} for name, (arr, of) in arrays.items()}
+
+
 def spread(us):
     """min / median / max (and the values, for short runs) of per-step µs."""
     if not us:
@@ -659,7 +727,8 @@ def main():
         sys.exit("bench.py: --backend gloo is only for --selftest (the GPU bench gathers over RCCL)")
     cfg = CONFIGS[a.config]
     cfg_idx = int(a.config[1:])
-    cpu_on = a.cpu_baseline and world == 1 and rank == 0
+    full = a.full  # every leg but the headline window runs only with --full
+    cpu_on = full and a.cpu_baseline and world == 1 and rank == 0
     cpu_multi = cpu_baseline_multi(a, cfg, cfg_idx) if cpu_on else None  # forks: before the GPU
     if distributed:
         torch.cuda.set_device(local)
@@ -749,7 +818,7 @@ def main():
     ring_req = max(1, a.ring if a.ring is not None else cfg.get("ring", 1)) if V == 1 else 1
     ctl_req = 0
     ring_ctl = a.ring_control if a.ring_control is not None else cfg.get("ring_control", 3)
-    if V == 1 and ring_ctl > 0:
+    if full and V == 1 and ring_ctl > 0:
         ctl_req = 1 if ring_req > 1 else ring_ctl  # the control: one view, or distinct ones
     slots = [dict(stack=stack, tex=tex, out=out)]  # the distinct resident views
 
@@ -771,6 +840,7 @@ def main():
     ctl_slots = ring_of(ctl_req) if ctl_req else []
     ring_R = len({sl["stack"].data_ptr() for sl in head_slots}) if V == 1 else 1
     ring = {"slots": head_slots, "i": 0}
+    last = [None]  # what the latest step's call returned (--dump-outputs)
 
     def one(at=None):
         """One step (the next, or step number ``at``: ring slot at % R, lane
@@ -785,9 +855,9 @@ def main():
         else:
             st_, tx_, o_, nx_ = stack, tex, out, nxt
         if pool is None:
-            eng.decode_triangulate(st_, n_cols, n_rows, texture=tx_, maps=maps, cloud=True,
-                                   xyz_dtype=torch.float32, poses=poses, fast_f32=head_fast, out=o_,
-                                   next_stack=nx_)
+            last[0] = eng.decode_triangulate(st_, n_cols, n_rows, texture=tx_, maps=maps, cloud=True,
+                                             xyz_dtype=torch.float32, poses=poses, fast_f32=head_fast, out=o_,
+                                             next_stack=nx_)
             return cur
         # resident inputs (wait_inputs=False); one view: its own outputs, else
         # the lane's (never read while the window runs)
@@ -795,6 +865,7 @@ def main():
                                       xyz_dtype=torch.float32, poses=poses, fast_f32=head_fast,
                                       wait_inputs=False, lane=at % S, next_stack=nx_, prepared=True,
                                       **({"out": o_} if V == 1 else {}))
+        last[0] = res
         return res["stream"]
 
     def run_steps(k):
@@ -892,8 +963,9 @@ def main():
     # Per-step HIP events cost ~5.7 us of GPU idle per step (same trace), so
     # the headline window has none; an identical window with one event per
     # step boundary follows immediately and gives the per-step spread.
-    evs = [torch.cuda.Event(enable_timing=True) for _ in range(a.steps + 1)]
-    snap = snap_alloc(out, V, maps) if a.verify else None
+    evs = [torch.cuda.Event(enable_timing=True) for _ in range(a.steps + 1)] if full else None
+    snap = snap_alloc(out, V, maps) if full and a.verify else None
+    dumped = None
     gc.collect()
     gc.disable()
     try:
@@ -932,7 +1004,9 @@ def main():
                     sj = snap_alloc(head_slots[k_s]["out"], V, maps)
                     snap_copy(sj, head_slots[k_s]["out"], cur)
                     lane_snaps.append((j, k_s, sj))
-        el_ev, step_us = timed(a.steps, evs)
+        if a.dump_outputs and rank == 0:  # the headline window's last step, before anything else runs
+            dumped = dump_outputs(a.dump_outputs, last[0])
+        el_ev, step_us = timed(a.steps, evs) if full else (None, None)
         # the control window: the same K steps over ctl_R distinct resident
         # views (or one, when the headline cycles several), after its own
         # pre-roll, captured and launched as the headline -- do the 256 MB
@@ -981,13 +1055,71 @@ def main():
         def gfn():
             _, _, counts = parallel.gather_cloud(out["xyz"][:n_loc], out["bgr"][:n_loc], dst=0)
             return counts
-    multi = gather_report(el_rank, n_loc, 15, dev, gfn, distributed)
-    if distributed:
+    multi = gather_report(el_rank, n_loc, 15, dev, gfn, distributed, timed_gather=full)
+    if distributed and full:
         multi["gather_path"] = ("sl_gather (the library's RCCL communicator)" if a.gather == "native"
                                 else "torch.distributed batch_isend_irecv (RCCL)")
-    if distributed and a.strong_leg and not (a.config == "c3" and a.scaling == "strong"):
+    if full and distributed and a.strong_leg and not (a.config == "c3" and a.scaling == "strong"):
         multi["strong_c3"] = strong_leg_report(a, world, rank, distributed, dev, 1920 * 1080,
                                                lambda views3: run_c3_leg(a, dev, views3))
+
+    px_step = V_total * H * W  # whole job: every rank's views
+    path_b = path_bytes(H, W, read_planes, n_pts / V, maps) * V
+    path_gbps = path_b / (el / a.steps) / 1e9
+
+    def headline():
+        """Rank 0's line of a plain run: the headline window and its workload
+        (--full adds the other legs' blocks to it)."""
+        return {
+            "metric": "decoded+triangulated px/s",
+            "value": px_step * a.steps / el,
+            "unit": "px/s",
+            "n_gpus": world,
+            "steps": a.steps,
+            "warmup": a.warmup,
+            "ms_per_step": 1e3 * el / a.steps,
+            "higher_is_better": True,
+            "scaling": a.scaling,
+            "vs_baseline": None,
+            "dtype": "u8+f32" if head_fast else "u8+f64",
+            "data": "synthetic",
+            "full": full,
+            "config": {"workload": f"BASELINE config {cfg_idx}: {V} x {W}x{H} view(s) per GPU per step ({a.scaling} scaling, {V_total} in all), "
+                                   f"{n_planes}-plane stacks (Gray {nc}+{n_planes // 2 - 1 - nc} bits + inverses), "
+                                   + ("col/row/mask maps + " if maps else "")
+                                   + "fp32 xyz/BGR cloud" + (" with turntable pose" if poses is not None else "")
+                                   + (f"; the steps cycle through {ring_R} distinct resident views (chained)"
+                                      if ring_R > 1 else ""),
+                       "views_per_gpu": V, "views_total": V_total, "H": H, "W": W, "projector": f"{Wp}x{Hp}",
+                       "parallelism": f"views sharded over {world} GPU(s)", "streams_per_gpu": S,
+                       "lane_stream_priority": lane_prio if S > 1 else None,
+                       "next_stats": bool(a.next_stats)},
+            "timing": {"preroll": pre,
+                       "window": window,
+                       "host_enqueue_ms": enq_ms,
+                       "host_enqueue_note": "host time to enqueue the headline window's K steps (of its wall "
+                                            "time): close to the wall time = the host, not the GPU, set the pace",
+                       "gc": "collected before the pre-roll, disabled through the windows",
+                       "ring_views": ring_R},
+            "roofline": {"bound": "hbm", "scope": "whole path per step: every kernel of the step",
+                         "achieved": path_gbps, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                         "frac": path_gbps / HBM_PEAK_GBS,
+                         "algorithmic_bytes_per_step": path_b,
+                         "bytes_note": f"SURVEY.md 8(d): {read_planes} stack planes read + 3 B/px BGR texture + "
+                                       "15 B/point (f32 xyz + BGR)" + (" + 9 B/px col/row/mask maps" if maps else "")
+                                       + "; time: the step's wall time (barrier + synchronize on both sides)"},
+            "points_per_view": n_pts / V,
+            "multi_gpu": multi,
+            "xyz_mode": XYZ_MODES[head_fast],
+            "dump_outputs": dumped,
+        }
+
+    if not full:
+        if rank == 0:
+            print(json.dumps(headline()))
+        if distributed:
+            dist.destroy_process_group()
+        return
 
     # per-kernel time: HIP events recorded by the library on the launch stream
     # around k_stats / k_decode / k_cloud, in a separate pass (events between
@@ -1086,8 +1218,6 @@ def main():
     cpu = cpu_baseline_single(a, cfg, cfg_idx, cpu_multi) if cpu_on else None
 
     if rank == 0:
-        px_step = V_total * H * W  # whole job: every rank's views
-        value = px_step * a.steps / el
         # the re-run figure only where the group's stack exceeds the 256 MB
         # Infinity Cache (else the re-runs would read it warm): in-step events
         rerun_ok = H * W * read_planes * v_last > 256 * 2 ** 20
@@ -1095,10 +1225,8 @@ def main():
         v_roof = v_last if rerun_ok else V
         ab = decode_bytes(H, W, read_planes, maps, decide) * v_roof
         achieved = ab / (dec_avg_ms * 1e-3) / 1e9
-        path_b = path_bytes(H, W, read_planes, n_pts / V, maps) * V
-        path_gbps = path_b / (el / a.steps) / 1e9
-        # PMC bytes (rocprofv3 FETCH_SIZE x 2 + WRITE_SIZE, MI355X_MICROARCH.md)
-        # of the same command, from a committed profile -- not measured here
+        # PMC bytes (rocprofv3 FETCH_SIZE x 2 + WRITE_SIZE) of the same
+        # command, from a committed profile -- not measured here
         traffic = traffic_k = None
         if a.traffic is None:
             a.traffic = os.path.join(REPO, TRAFFIC_DIR, f"traffic_{a.config}.json")
@@ -1114,86 +1242,54 @@ def main():
             except (OSError, ValueError):
                 traffic = traffic_k = None
         slots = ("k_decode", "k_stats", "k_cloud") if decide else ("k_decode", "k_count", "k_cloud")
-        res = {
-            "metric": "decoded+triangulated px/s",
-            "value": value,
-            "unit": "px/s",
-            "n_gpus": world,
-            "steps": a.steps,
-            "warmup": a.warmup,
-            "ms_per_step": 1e3 * el / a.steps,
-            "higher_is_better": True,
-            "scaling": a.scaling,
-            "vs_baseline": None,
-            "dtype": "u8+f32" if head_fast else "u8+f64",
-            "data": "synthetic",
-            "config": {"workload": f"BASELINE config {cfg_idx}: {V} x {W}x{H} view(s) per GPU per step ({a.scaling} scaling, {V_total} in all), "
-                                   f"{n_planes}-plane stacks (Gray {nc}+{n_planes // 2 - 1 - nc} bits + inverses), "
-                                   + ("col/row/mask maps + " if maps else "")
-                                   + "fp32 xyz/BGR cloud" + (" with turntable pose" if poses is not None else "")
-                                   + (f"; the steps cycle through {ring_R} distinct resident views (chained)"
-                                      if ring_R > 1 else ""),
-                       "views_per_gpu": V, "views_total": V_total, "H": H, "W": W, "projector": f"{Wp}x{Hp}",
-                       "parallelism": f"views sharded over {world} GPU(s)", "streams_per_gpu": S,
-                       "lane_stream_priority": lane_prio if S > 1 else None,
-                       "next_stats": bool(a.next_stats)},
-            "timing": {"preroll": pre,
-                       "step_us": spread(step_us),
-                       "step_us_note": "HIP events at every step boundary, on the step's stream; intervals "
-                                       "between the sorted completion times (several lanes: steps complete on "
-                                       "different streams), in an identical window right after the timed one "
-                                       "(the events add ~5.7 us of idle per step: not in the headline window)",
-                       "ms_per_step_with_events": 1e3 * el_ev / a.steps,
-                       "window": window,
-                       "host_enqueue_ms": enq_ms,
-                       "host_enqueue_note": "host time to enqueue the headline window's K steps (of its wall "
-                                            "time): close to the wall time = the host, not the GPU, set the pace",
-                       "gc": "collected before the pre-roll, disabled through the windows",
-                       "ring_views": ring_R,
-                       "distinct_views": None if distinct is None else {
-                           "views": distinct["views"], "ms_per_step": distinct["ms_per_step"],
-                           "ratio_to_headline": distinct["ms_per_step"] / (1e3 * el / a.steps),
-                           "window": distinct["window"], "preroll": distinct["preroll"],
-                           "resident_input_bytes": distinct["resident_input_bytes"],
-                           "note": "the same K chained steps cycling through this many distinct resident views "
-                                   "(stack, texture and outputs each), after their own pre-roll"
-                                   + ("; one view: what of its texture, records and outputs the 256 MiB "
-                                      "Infinity Cache keeps may serve the next step" if distinct["views"] == 1
-                                      else "; their inputs exceed the 256 MiB Infinity Cache, so no line of a "
-                                           "view's inputs survives to its next step"
-                                      if distinct["resident_input_bytes"] > 2 ** 28
-                                      else "; their inputs fit the 256 MiB Infinity Cache, so the control does "
-                                           "not exclude cache hits from step to step")
-                                   + "; verified like the headline (verification.distinct_views_window)"}},
-            "roofline": {"bound": "hbm", "scope": "whole path per step: every kernel of the step",
-                         "achieved": path_gbps, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": path_gbps / HBM_PEAK_GBS, "traffic": traffic,
-                         "traffic_source": (f"PMC, {os.path.relpath(a.traffic, REPO)} (committed rocprofv3 "
-                                            "FETCH_SIZE / WRITE_SIZE passes of this step's kernels, per step, "
-                                            "each counter calibrated on known byte counts of the kernels' "
-                                            "access widths: scripts/micro/store_calib)")
-                                           if traffic is not None else None,
-                         "algorithmic_bytes_per_step": path_b,
-                         "bytes_note": f"SURVEY.md 8(d): {read_planes} stack planes read + 3 B/px BGR texture + "
-                                       "15 B/point (f32 xyz + BGR)" + (" + 9 B/px col/row/mask maps" if maps else "")
-                                       + "; time: the step's wall time (barrier + synchronize on both sides)",
-                         "dominant_kernel": {
-                             "name": "k_decode", "achieved": achieved, "frac": achieved / HBM_PEAK_GBS,
-                             "avg_ms": dec_avg_ms, "algorithmic_bytes_per_launch": ab, "traffic": traffic_k,
-                             "bytes_note": f"{read_planes} stack planes read"
-                                           + ((" + col/row int32" + (" + mask" if decide else "") + " maps written")
-                                              if maps else "")
-                                           + f", per launch over {v_roof} view(s) (records, point bits are "
-                                             "overhead); duration: "
-                                           + ("HIP events around back-to-back re-runs of the launch "
-                                              "(sl_time_kernels)" if rerun_ok
-                                              else "HIP events around the kernel inside the steps"),
-                             "lanes": S,
-                             "lanes_note": None if S == 1 else (
-                                 f"the window keeps {S} calls in flight on {S} streams, and their kernels run "
-                                 "side by side: a rocprofv3 per-dispatch average of this command spans the time a "
-                                 "launch shares the chip with the other lanes' launches (up to "
-                                 f"{S}x this figure); --streams 1 gives the isolated dispatch (DESIGN.md 6.2)")}},
+        res = headline()
+        res["timing"].update({
+            "step_us": spread(step_us),
+            "step_us_note": "HIP events at every step boundary, on the step's stream; intervals "
+                            "between the sorted completion times (several lanes: steps complete on "
+                            "different streams), in an identical window right after the timed one "
+                            "(the events add ~5.7 us of idle per step: not in the headline window)",
+            "ms_per_step_with_events": 1e3 * el_ev / a.steps,
+            "distinct_views": None if distinct is None else {
+                "views": distinct["views"], "ms_per_step": distinct["ms_per_step"],
+                "ratio_to_headline": distinct["ms_per_step"] / (1e3 * el / a.steps),
+                "window": distinct["window"], "preroll": distinct["preroll"],
+                "resident_input_bytes": distinct["resident_input_bytes"],
+                "note": "the same K chained steps cycling through this many distinct resident views "
+                        "(stack, texture and outputs each), after their own pre-roll"
+                        + ("; one view: what of its texture, records and outputs the 256 MiB "
+                           "Infinity Cache keeps may serve the next step" if distinct["views"] == 1
+                           else "; their inputs exceed the 256 MiB Infinity Cache, so no line of a "
+                                "view's inputs survives to its next step"
+                           if distinct["resident_input_bytes"] > 2 ** 28
+                           else "; their inputs fit the 256 MiB Infinity Cache, so the control does "
+                                "not exclude cache hits from step to step")
+                        + "; verified like the headline (verification.distinct_views_window)"}})
+        res["roofline"].update({
+            "traffic": traffic,
+            "traffic_source": (f"PMC, {os.path.relpath(a.traffic, REPO)} (committed rocprofv3 "
+                               "FETCH_SIZE / WRITE_SIZE passes of this step's kernels, per step, "
+                               "each counter calibrated on known byte counts of the kernels' "
+                               "access widths: scripts/micro/store_calib)")
+                              if traffic is not None else None,
+            "dominant_kernel": {
+                "name": "k_decode", "achieved": achieved, "frac": achieved / HBM_PEAK_GBS,
+                "avg_ms": dec_avg_ms, "algorithmic_bytes_per_launch": ab, "traffic": traffic_k,
+                "bytes_note": f"{read_planes} stack planes read"
+                              + ((" + col/row int32" + (" + mask" if decide else "") + " maps written")
+                                 if maps else "")
+                              + f", per launch over {v_roof} view(s) (records, point bits are "
+                                "overhead); duration: "
+                              + ("HIP events around back-to-back re-runs of the launch "
+                                 "(sl_time_kernels)" if rerun_ok
+                                 else "HIP events around the kernel inside the steps"),
+                "lanes": S,
+                "lanes_note": None if S == 1 else (
+                    f"the window keeps {S} calls in flight on {S} streams, and their kernels run "
+                    "side by side: a rocprofv3 per-dispatch average of this command spans the time a "
+                    "launch shares the chip with the other lanes' launches (up to "
+                    f"{S}x this figure); --streams 1 gives the isolated dispatch (DESIGN.md 6.2)")}})
+        res.update({
             "path": {"kind": ("k_decode (mask, point decision) + k_cloud (+ the next call's histogram pass: "
                               "sl_stack_next; the first call alone runs k_stats)" if a.next_stats
                               else "k_stats + k_decode (mask, point decision) + k_cloud") if decide
@@ -1211,12 +1307,9 @@ def main():
             "verified": verified,
             "verification": verification,
             "single_shot": shots,
-            "points_per_view": n_pts / V,
             "cloud_only_px_per_s": None if el_cloud is None else px_step * a.steps / el_cloud,
-            "multi_gpu": multi,
-            "xyz_mode": XYZ_MODES[head_fast],
             "alt_xyz_mode": alt,
-        }
+        })
         print(json.dumps(res))
     if distributed:
         dist.destroy_process_group()

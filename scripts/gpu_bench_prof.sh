@@ -6,9 +6,9 @@ export TMPDIR=/tmp
 O=gpurun_out/bp
 mkdir -p $O
 CFG="${1:-c2}"
-timeout -k 10 300 python -u bench.py --config $CFG --steps 20 --warmup 5 --cpu-seconds 10 > $O/bench.json 2> $O/bench.err || exit $?
+timeout -k 10 300 python -u bench.py --full --config $CFG --steps 20 --warmup 5 --cpu-seconds 10 > $O/bench.json 2> $O/bench.err || exit $?
 tail -1 $O/bench.json
-APP="python -u bench.py --config $CFG --steps 10 --warmup 3 --no-cpu-baseline"
+APP="python -u bench.py --full --config $CFG --steps 10 --warmup 3 --no-cpu-baseline"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o trace -- $APP > $O/trace.log 2>&1 || exit $?
 timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/fetch -o fetch -- $APP > $O/fetch.log 2>&1 || exit $?
 timeout -s KILL 120 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/write -o write -- $APP > $O/write.log 2>&1 || exit $?

@@ -1,13 +1,14 @@
 set -u
-cd "$GRAFT_REPO_ROOT"
-mkdir -p gpurun_out
-timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread > gpurun_out/pytest_gpu.log 2>&1
+cd "$(dirname "$0")/.."
+OUT="${OUT:-build/gpu_check}"
+mkdir -p "$OUT"
+timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread >"$OUT/pytest_gpu.log" 2>&1
 rc=$?
 echo "pytest rc=$rc"
-tail -5 gpurun_out/pytest_gpu.log
+tail -5 "$OUT/pytest_gpu.log"
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
-timeout -k 10 300 python -u bench.py --steps 20 --warmup 5 --cpu-seconds 8 > gpurun_out/bench.log 2>&1
+timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 5 --cpu-seconds 8 > "$OUT/bench.log" 2>&1
 rc2=$?
 echo "bench rc=$rc2"
-tail -3 gpurun_out/bench.log
+tail -3 "$OUT/bench.log"
 exit $rc2

@@ -122,6 +122,67 @@ def test_bench_defaults_next_stats_and_graph():
     assert not a.next_stats and not a.graph and not a.verify and not a.strong_leg and a.single_shot == 0
 
 
+def test_full_and_dump_outputs_switches():
+    """A plain run is the headline window alone: --full (off by default) turns
+    the other legs on, each still behind its own switch; --dump-outputs names
+    a directory."""
+    import bench
+    a = bench.parse([])
+    assert a.full is False and a.dump_outputs is None
+    a = bench.parse(["--full", "--dump-outputs", "d", "--steps", "7"])
+    assert a.full is True and a.dump_outputs == "d" and a.steps == 7 and a.verify and a.cpu_baseline
+
+
+def test_dump_outputs_writes_float_arrays_and_seeded_samples(tmp_path, monkeypatch):
+    """bench.dump_outputs on a stand-in result: small arrays whole, arrays
+    over the per-array budget as the same sorted sample on every call, maps
+    sampled at the same elements and xyz / bgr at the same rows; only the
+    cloud's view_offsets[-1] rows count."""
+    import numpy as np
+    import torch
+
+    import bench
+    from structured_light_for_3d_model_replication_amd import core
+    V, H, W, n = 2, 30, 50, 1700
+    g = torch.Generator().manual_seed(5)
+    col = torch.randint(0, 2048, (V, H, W), dtype=torch.int32, generator=g)
+    res = {"col_map": col, "row_map": col + 1, "mask": col % 2 == 0,
+           "cloud": core.Cloud(torch.randn((V * H * W, 3), generator=g), torch.randint(0, 256, (V * H * W, 3), generator=g).to(torch.uint8),
+                               torch.tensor([0, 700, n]))}
+
+    def load(d):
+        return {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+    info = bench.dump_outputs(str(tmp_path / "whole"), res)
+    w = load(tmp_path / "whole")
+    assert sorted(w) == ["bgr", "col_map", "mask", "row_map", "view_offsets", "xyz"]
+    assert all(v.dtype == (np.float64 if k == "view_offsets" else np.float32) for k, v in w.items())
+    np.testing.assert_array_equal(w["col_map"], col.numpy())
+    np.testing.assert_array_equal(w["mask"], (col % 2 == 0).numpy())
+    np.testing.assert_array_equal(w["xyz"], res["cloud"].xyz[:n].numpy())
+    np.testing.assert_array_equal(w["bgr"], res["cloud"].bgr[:n].numpy())
+    np.testing.assert_array_equal(w["view_offsets"], [0, 700, n])
+    assert info["xyz"] == {"shape": [n, 3], "of": n}
+
+    monkeypatch.setattr(bench, "DUMP_ARRAY_BYTES", 4 * 600)  # 600 map elements, 200 cloud rows
+    bench.dump_outputs(str(tmp_path / "s1"), res)
+    bench.dump_outputs(str(tmp_path / "s2"), res)
+    s1, s2 = load(tmp_path / "s1"), load(tmp_path / "s2")
+    for k in s1:
+        np.testing.assert_array_equal(s1[k], s2[k])
+    assert s1["col_map"].shape == (600,) and s1["xyz"].shape == (200, 3) and s1["bgr"].shape == (200, 3)
+    np.testing.assert_array_equal(s1["row_map"], s1["col_map"] + 1)  # the same elements
+    np.testing.assert_array_equal(s1["mask"], s1["col_map"] % 2 == 0)
+    # the sample is a sorted subset of the whole array's elements / rows
+    flat = col.numpy().reshape(-1)
+    idx, rows = bench.dump_sample(flat.size, 1), bench.dump_sample(n, 3)
+    assert len(np.unique(idx)) == 600 and np.all(np.diff(idx) > 0) and 0 <= idx[0] and idx[-1] < flat.size
+    assert len(np.unique(rows)) == 200 and np.all(np.diff(rows) > 0) and 0 <= rows[0] and rows[-1] < n
+    assert bench.dump_sample(600, 1) is None and bench.dump_sample(200, 3) is None
+    np.testing.assert_array_equal(s1["col_map"], flat[idx])
+    np.testing.assert_array_equal(s1["xyz"], res["cloud"].xyz[:n].numpy()[rows])
+    np.testing.assert_array_equal(s1["bgr"], res["cloud"].bgr[:n].numpy()[rows])
+
+
 def test_committed_traffic_profiles_match_the_configs():
     """bench.py attaches <bench.TRAFFIC_DIR>/traffic_<config>.json (the
     directory bench.py itself reads by default) to a line only when the profile's workload is the line's (config, views per GPU,
