@@ -399,6 +399,42 @@ int sl_ransac_feature_matching(sl_ctx* ctx, const double* source, int64_t n_src,
                                uint64_t seed, double* transformation, double* fitness, double* inlier_rmse,
                                int* iterations, int* validations, int64_t* n_corres, void* stream);
 
+/* ---- per-view clean-up (ProcessingLogic.remove_background, processing.py:25-52) ----
+ * pcd.segment_plane(distance_threshold, ransac_n, num_iterations, probability):
+ * Open3D's PointCloud::SegmentPlane as one thread runs it, restated (parity
+ * vs Open3D is unpinned: not in this image; tests/plane_oracle.py is the CPU
+ * restatement, bit-identical; csrc/slplane.inl states the arithmetic and the
+ * one summation order).  Iteration i draws points splitmix64(seed +
+ * (ransac_n i + k + 1) * 0x9E3779B97F4A7C15) (k < ransac_n; duplicates are not
+ * redrawn -- Open3D samples without replacement), fits a plane (3 points: the
+ * normalised cross product, a zero one skipped; 4..16: GetPlaneFromPoints),
+ * counts the points with |((a x + b y) + c z) + d| < distance_threshold; the
+ * best by (count, then lower rmse = err / sqrt(count)) sets the break
+ * iteration k = min(log(1 - probability) / log(1 - fitness^ransac_n),
+ * num_iterations) (0 for fitness 1); iteration i runs iff i <= k.  Hypotheses
+ * are scored on the GPU `batch` at a time (0: 64, the fastest measured at 4K;
+ * any batch gives the same bits) and walked in iteration order.
+ * xyz: device f64 [n][3].  Outputs: plane_model host[4] = GetPlaneFromPoints
+ * of the best hypothesis's inliers (f64 sums in the fixed order of
+ * slplane.inl); their indices, ascending -> inlier_index (device, capacity
+ * n), the count -> *n_inliers; the other points' indices, ascending ->
+ * rest_index (device, capacity n; may be NULL; n - *n_inliers of them);
+ * *iterations = iterations run (may be NULL).  No hypothesis with an inlier
+ * (collinear clouds, num_iterations 0): plane (0, 0, 0, 0) and no inliers
+ * (Open3D: the same zero plane, from its initial best).  SL_EINVAL for
+ * ransac_n < 3 or > 16, n < ransac_n, n >= 2^31, num_iterations < 0,
+ * probability outside (0, 1).  Blocking on `stream`. */
+int sl_segment_plane(sl_ctx* ctx, const double* xyz, int64_t n, double distance_threshold, int ransac_n,
+                     int num_iterations, double probability, uint64_t seed, int batch, double* plane_model,
+                     int64_t* inlier_index, int64_t* n_inliers, int64_t* rest_index, int* iterations, void* stream);
+
+/* The indices of [0, n) that index[0..m) (device) does not list, ascending ->
+ * out_index (device, capacity n), their count -> *out_n: what
+ * select_by_index(index, invert=true) gathers.  Entries outside [0, n) are
+ * ignored; duplicates are allowed.  Blocking on `stream`. */
+int sl_index_complement(sl_ctx* ctx, const int64_t* index, int64_t m, int64_t n, int64_t* out_index, int64_t* out_n,
+                        void* stream);
+
 /* Release the scratch buffers the merge entry points keep pooled for `device`
  * (kept otherwise for the process's lifetime, at most 16 GiB per device);
  * the bytes released -> *released_bytes (may be NULL). */

@@ -2110,3 +2110,5 @@ int sl_merge_pool_trim(int device, int64_t* released_bytes) {
 
 // global registration (FPFH, feature matching, RANSAC): the same translation unit
 #include "slreg.inl"
+// plane RANSAC of the per-view background removal (uses slreg.inl's draw)
+#include "slplane.inl"

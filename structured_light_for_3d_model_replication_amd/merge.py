@@ -24,6 +24,12 @@ oracle/registration_oracle.py and oracle/merge_oracle.py restate them.  With
 the relative pose between the two views.
 ``merge_pro_360_posed`` skips registration and takes the poses as they are
 (the same ones ``Reconstructor.decode_triangulate`` applies inside k_cloud).
+
+Clean-up before the merge.  ``segment_plane`` (sl_segment_plane,
+csrc/slplane.inl) is the plane RANSAC of ``remove_background``
+(processing.py:25-52); ``processing.py`` of this package is the drop-in for the
+reference's ``ProcessingLogic`` built on it.  Parity vs Open3D unpinned;
+tests/plane_oracle.py restates it.
 """
 from __future__ import annotations
 
@@ -104,21 +110,64 @@ def remove_statistical_outlier(points, nb_neighbors: int = 20, std_ratio: float 
     return ind[: k.value], avg[:n]
 
 
-def select_by_index(points, colors, ind, *, device=None):
-    """PointCloud.select_by_index -> (points, colors | None) on the device."""
+def select_by_index(points, colors, ind, invert: bool = False, *, device=None):
+    """PointCloud.select_by_index(ind, invert) -> (points, colors | None) on the
+    device; ``invert=True`` selects the points ``ind`` does not list, in their
+    original order."""
     eng = _engine(device)
     P = _f64(points, eng.device)
     C = _u8(colors, eng.device, P.shape[0])
     I = torch.as_tensor(ind).to(device=eng.device, dtype=torch.int64).contiguous()
-    m = I.shape[0]
-    if m and (int(I.min()) < 0 or int(I.max()) >= P.shape[0]):
+    if I.shape[0] and (int(I.min()) < 0 or int(I.max()) >= P.shape[0]):
         raise IndexError("index out of range")
+    if invert:  # the complement's index list (sl_index_complement); the gather below is the same kernel
+        n = P.shape[0]
+        rest = torch.empty(max(n, 1), dtype=torch.int64, device=eng.device)
+        k = ctypes.c_int64()
+        with eng._lock:
+            _lib.check(eng._L.sl_index_complement(eng._ctx, I.data_ptr() if I.shape[0] else None, I.shape[0], n,
+                                                  rest.data_ptr(), ctypes.byref(k), eng._stream(None)),
+                       eng._ctx, "sl_index_complement")
+        I = rest[: k.value]
+    m = I.shape[0]
     out = torch.empty((max(m, 1), 3), dtype=torch.float64, device=eng.device)
     oc = None if C is None else torch.empty((max(m, 1), 3), dtype=torch.uint8, device=eng.device)
     with eng._lock:
         _lib.check(eng._L.sl_select_by_index(eng._ctx, _ptr(P), _ptr(C), I.data_ptr(), m, out.data_ptr(), _ptr(oc),
                                              eng._stream(None)), eng._ctx, "sl_select_by_index")
     return out[:m], (None if oc is None else oc[:m])
+
+
+def segment_plane(points, distance_threshold, ransac_n: int = 3, num_iterations: int = 100,
+                  probability: float = 0.99999999, *, seed: int = 0, batch: int = 0, device=None):
+    """PointCloud.segment_plane(distance_threshold, ransac_n, num_iterations,
+    probability) (processing.py:37-39; Open3D's defaults) on the GPU
+    (sl_segment_plane) -> (plane_model numpy [4], inliers int64 [K] ascending on
+    the device, info).  ``info``: ``iterations`` (RANSAC iterations run before
+    the early exit) and ``rest`` (the other points' indices, ascending, on the
+    device: what ``select_by_index(inliers, invert=True)`` selects).
+
+    Open3D's algorithm restated; parity with Open3D is unpinned (not in this
+    image) and tests/plane_oracle.py is the bit-identical CPU restatement.  Two
+    documented deviations: ``seed`` fixes a splitmix64 draw that may repeat a
+    point within a sample (Open3D samples without replacement), and a cloud on
+    which no hypothesis has an inlier returns the zero plane and no inliers.
+    ``batch`` (hypotheses per GPU pass; 0: the default, 64) does not
+    change the result."""
+    eng = _engine(device)
+    P = _f64(points, eng.device)
+    n = P.shape[0]
+    inl = torch.empty(max(n, 1), dtype=torch.int64, device=eng.device)
+    rest = torch.empty(max(n, 1), dtype=torch.int64, device=eng.device)
+    plane = np.zeros(4)
+    k, it = ctypes.c_int64(), ctypes.c_int()
+    with eng._lock:
+        _lib.check(eng._L.sl_segment_plane(
+            eng._ctx, _ptr(P) if n else None, n, float(distance_threshold), int(ransac_n), int(num_iterations),
+            float(probability), int(seed) & ((1 << 64) - 1), int(batch),
+            plane.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), inl.data_ptr(), ctypes.byref(k), rest.data_ptr(),
+            ctypes.byref(it), eng._stream(None)), eng._ctx, "sl_segment_plane")
+    return plane, inl[: k.value], {"iterations": it.value, "rest": rest[: n - k.value]}
 
 
 def transform(points, pose, *, device=None) -> torch.Tensor:

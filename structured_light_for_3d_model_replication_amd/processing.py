@@ -1,0 +1,175 @@
+"""Drop-in for the reference's ``server/processing.py`` (``ProcessingLogic``).
+
+The reference's scanner works in four steps -- scan, clean each view, merge,
+mesh -- and ``ProcessingLogic`` holds the last three as static methods over
+Open3D.  This module keeps their names, arguments, defaults, prints and
+errors, and runs them on the GPU through ``merge`` (libslgpu.so):
+
+* ``remove_background`` (processing.py:25-52): ``segment_plane`` +
+  ``select_by_index(invert=True)`` -> ``merge.segment_plane`` (sl_segment_plane,
+  the plane RANSAC of csrc/slplane.inl) and the gather kernel.  One extra
+  keyword-only argument, ``seed``: Open3D's draw is unseeded.
+* ``remove_outliers`` (:55-76) -> ``merge.remove_statistical_outlier`` +
+  ``merge.select_by_index``.
+* ``preprocess_point_cloud``, ``execute_global_registration`` and
+  ``merge_pro_360`` delegate to ``merge``.
+* ``reconstruct_stl`` and ``mesh_360`` (Poisson meshing) are NOT provided.
+
+Without Open3D, "a point cloud object" is a ``Cloud(points, colors)`` of
+device tensors (f64 [N, 3], BGR u8 [N, 3] or None).  It is accepted wherever
+the reference accepts a path or an object and returned when ``return_obj`` is
+set.  Files are read with ``ply.read_ply`` and written with
+``ply.save_ply_open3d`` (the layout o3d.io.write_point_cloud writes).  A file
+that cannot be parsed loads as an empty cloud, as o3d.io.read_point_cloud
+returns one.
+
+The algorithms restate Open3D's; parity with Open3D is unpinned (see merge.py
+and csrc/slplane.inl for the two documented deviations of the plane RANSAC).
+
+``process_folder`` is the batch loop of page 2 of the reference GUI
+(gui.py:595-618); ``python -m structured_light_for_3d_model_replication_amd.
+processing --input DIR --output DIR`` runs it.
+"""
+from __future__ import annotations
+
+import argparse
+import glob
+import os
+
+import numpy as np
+import torch
+
+from . import merge, ply
+
+
+class Cloud:
+    """A point cloud on the device: ``points`` f64 [N, 3], ``colors`` BGR u8 [N, 3] or None."""
+
+    def __init__(self, points, colors=None):
+        self.points = points
+        self.colors = colors
+
+    def has_points(self) -> bool:
+        return len(self.points) > 0
+
+    def __len__(self) -> int:
+        return len(self.points)
+
+
+def _write(path, cloud: Cloud) -> None:
+    C = cloud.colors if cloud.colors is not None else torch.zeros((len(cloud), 3), dtype=torch.uint8)
+    ply.save_ply_open3d(cloud.points.cpu().numpy(), C.cpu().numpy(), path)
+
+
+class ProcessingLogic:
+    @staticmethod
+    def _load_pcd(input_data):
+        if isinstance(input_data, str):
+            if not os.path.exists(input_data):
+                raise FileNotFoundError(f"Input file not found: {input_data}")
+            try:
+                P, C = ply.read_ply(input_data)
+            except (ValueError, KeyError, IndexError):  # read_point_cloud: a warning and an empty cloud
+                P, C = np.zeros((0, 3)), np.zeros((0, 3), np.uint8)
+            dev = merge._engine(None).device
+            return Cloud(torch.from_numpy(np.ascontiguousarray(P, dtype=np.float64)).to(dev),
+                         torch.from_numpy(np.ascontiguousarray(C)).to(dev))
+        return input_data
+
+    @staticmethod
+    def remove_background(input_data, output_path=None, distance_threshold=50, ransac_n=3, num_iterations=1000,
+                          return_obj=False, *, seed=0):
+        print("[BG Remove] Processing...")
+        pcd = ProcessingLogic._load_pcd(input_data)
+        if not pcd.has_points():
+            raise ValueError("Point cloud is empty.")
+        _, _, info = merge.segment_plane(pcd.points, distance_threshold, ransac_n=ransac_n,
+                                         num_iterations=num_iterations, seed=seed, device=pcd.points.device)
+        object_cloud = Cloud(*merge.select_by_index(pcd.points, pcd.colors, info["rest"], device=pcd.points.device))
+        print(f"[BG Remove] Original: {len(pcd.points)}, Remaining: {len(object_cloud.points)} pts")
+        if output_path:
+            _write(output_path, object_cloud)
+            print(f"[BG Remove] Saved to {output_path}")
+        return object_cloud if return_obj else None
+
+    @staticmethod
+    def remove_outliers(input_data, output_path=None, nb_neighbors=20, std_ratio=2.0, return_obj=False):
+        print("[Outlier] Processing...")
+        pcd = ProcessingLogic._load_pcd(input_data)
+        if not pcd.has_points():
+            raise ValueError("Point cloud is empty.")
+        ind, _ = merge.remove_statistical_outlier(pcd.points, nb_neighbors=nb_neighbors, std_ratio=std_ratio,
+                                                  device=pcd.points.device)
+        inlier_cloud = Cloud(*merge.select_by_index(pcd.points, pcd.colors, ind, device=pcd.points.device))
+        print(f"[Outlier] Keeping: {len(inlier_cloud.points)} pts")
+        if output_path:
+            _write(output_path, inlier_cloud)
+            print(f"[Outlier] Saved to {output_path}")
+        return inlier_cloud if return_obj else None
+
+    @staticmethod
+    def preprocess_point_cloud(pcd, voxel_size):
+        """-> (down-sampled Cloud with ``.normals``, its FPFH features [M, 33])."""
+        pcd = ProcessingLogic._load_pcd(pcd)
+        Pd, Nd, Fd = merge.preprocess_point_cloud(pcd.points, voxel_size, device=pcd.points.device)
+        down = Cloud(Pd)
+        down.normals = Nd
+        return down, Fd
+
+    @staticmethod
+    def execute_global_registration(source_down, target_down, source_fpfh, target_fpfh, voxel_size):
+        return merge.execute_global_registration(source_down.points, target_down.points, source_fpfh, target_fpfh,
+                                                 voxel_size, device=source_down.points.device)
+
+    @staticmethod
+    def merge_pro_360(input_folder, output_path, voxel_size=0.02):
+        merge.merge_pro_360(input_folder, output_path, voxel_size)
+
+
+def process_folder(in_dir, out_dir, *, bg_dist=50, bg_ransac_n=3, bg_iterations=1000, nb_neighbors=20,
+                   std_ratio=2.0):
+    """The batch loop of the reference GUI's page 2 (gui.py:595-618): every
+    ``*.ply`` of ``in_dir`` through remove_background and remove_outliers into
+    ``out_dir/<name>_processed.ply``; a file's error is printed and counted,
+    not raised.  -> (count, errors)."""
+    if not os.path.exists(out_dir):
+        os.makedirs(out_dir)
+    count = 0
+    errors = 0
+    for fpath in glob.glob(os.path.join(in_dir, "*.ply")):
+        fname = os.path.basename(fpath)
+        out_path = os.path.join(out_dir, fname.replace(".ply", "_processed.ply"))
+        print(f"[Task] Processing {fname}...")
+        try:
+            pcd = ProcessingLogic.remove_background(fpath, distance_threshold=bg_dist, ransac_n=bg_ransac_n,
+                                                    num_iterations=bg_iterations, return_obj=True)
+            pcd = ProcessingLogic.remove_outliers(pcd, nb_neighbors=nb_neighbors, std_ratio=std_ratio,
+                                                  return_obj=True)
+            _write(out_path, pcd)
+            print(f"[Task] Saved {out_path}")
+            count += 1
+        except Exception as e:  # noqa: BLE001  (the reference's loop catches everything per file)
+            print(f"[Task] Error processing {fname}: {e}")
+            errors += 1
+    return count, errors
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser(description="Background and outlier removal of every .ply in a folder")
+    ap.add_argument("--input", required=True)
+    ap.add_argument("--output", required=True)
+    ap.add_argument("--bg-dist", type=float, default=50)
+    ap.add_argument("--bg-ransac-n", type=int, default=3)
+    ap.add_argument("--bg-iterations", type=int, default=1000)
+    ap.add_argument("--nb-neighbors", type=int, default=20)
+    ap.add_argument("--std-ratio", type=float, default=2.0)
+    a = ap.parse_args(argv)
+    count, errors = process_folder(a.input, a.output, bg_dist=a.bg_dist, bg_ransac_n=a.bg_ransac_n,
+                                   bg_iterations=a.bg_iterations, nb_neighbors=a.nb_neighbors,
+                                   std_ratio=a.std_ratio)
+    print(f"Pipeline Completed.\nProcessed: {count}\nErrors: {errors}\nSaved to: {a.output}")
+    return 0 if errors == 0 else 1
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

@@ -1,0 +1,198 @@
+"""The per-view clean-up on the GPU: sl_segment_plane (csrc/slplane.inl) against
+tests/plane_oracle.py bit for bit, and the ``processing`` drop-in built on it.
+Open3D is not installed: parity with Open3D is unpinned; the oracle restates
+its SegmentPlane with the two documented deviations (seeded draw that may
+repeat a point; zero plane when nothing ever becomes the best)."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from tests import plane_oracle as po
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def mg():
+    from structured_light_for_3d_model_replication_amd import merge
+    return merge
+
+
+@pytest.fixture(scope="module")
+def pr():
+    from structured_light_for_3d_model_replication_amd import processing
+    return processing
+
+
+@pytest.fixture(scope="module")
+def wall():
+    return po.wall_scene()[0]
+
+
+def _same(mg, P, thr, rn, iters, seed=7, batch=0):
+    model, inl, info = mg.segment_plane(P, thr, rn, iters, seed=seed, batch=batch)
+    em, ei, eit = po.segment_plane(P, thr, rn, iters, seed=seed)
+    assert info["iterations"] == eit
+    np.testing.assert_array_equal(inl.cpu().numpy(), ei)
+    np.testing.assert_array_equal(model, em)
+    rest = np.setdiff1d(np.arange(len(P)), ei)
+    np.testing.assert_array_equal(info["rest"].cpu().numpy(), rest)
+    return eit, len(ei)
+
+
+def test_wall_scene(mg, wall):
+    it, k = _same(mg, wall, 10.0, 3, 1000)
+    assert it < 1000 and k > 0.5 * len(wall)
+
+
+def test_wall_30_percent(mg):
+    it, _ = _same(mg, po.wall_scene(5001, 0.3)[0], 10.0, 3, 1000)
+    assert it < 1000  # P(3 wall points) = 0.027: k = ln(1e-8) / ln(1 - 0.027) = 672 < 1000
+
+
+@pytest.mark.parametrize("n", [257, 3, 4097])
+def test_small_and_chunk_edge(mg, n):
+    _same(mg, po.wall_scene(n, 0.6)[0], 10.0, 3, 1000)
+
+
+def test_scatter_never_exits_early(mg):
+    it, _ = _same(mg, po.scatter_scene(4099), 2.0, 3, 300)
+    assert it == 300
+
+
+def test_lattice_count_ties(mg):
+    # many hypotheses reach the same count: the rmse tie-break decides
+    P = po.lattice_scene()
+    _same(mg, P, 0.25, 3, 400)
+    best = [po.hypothesis(P, 7, i, 3) for i in range(400)]
+    counts = [int((po.distances(P, pl) < 0.25).sum()) for pl in best if pl is not None]
+    assert counts.count(max(counts)) > 1
+
+
+def test_ransac_n_5(mg, wall):
+    _same(mg, wall, 10.0, 5, 1000)
+
+
+def test_many_chunks(mg):
+    it, k = _same(mg, po.wall_scene(300_000, 0.6)[0], 10.0, 3, 1000)
+    assert it < 1000 and k > 150_000
+
+
+def test_batch_size_does_not_change_the_result(mg, wall):
+    ref = mg.segment_plane(wall, 10.0, 3, 1000, seed=7)
+    for batch in (1, 5, 64):
+        model, inl, info = mg.segment_plane(wall, 10.0, 3, 1000, seed=7, batch=batch)
+        np.testing.assert_array_equal(model, ref[0])
+        assert torch.equal(inl, ref[1]) and info["iterations"] == ref[2]["iterations"]
+
+
+def test_collinear_points(mg):
+    P = np.outer(np.arange(50.0), [1.0, 2.0, 3.0])
+    model, inl, info = mg.segment_plane(P, 1.0, 3, 50, seed=1)
+    assert np.array_equal(model, np.zeros(4)) and len(inl) == 0 and info["iterations"] == 50
+    np.testing.assert_array_equal(info["rest"].cpu().numpy(), np.arange(50))
+
+
+def test_bad_arguments(mg):
+    P = po.scatter_scene(10)
+    with pytest.raises(ValueError):
+        mg.segment_plane(P, 1.0, ransac_n=2)
+    with pytest.raises(ValueError):
+        mg.segment_plane(P[:2], 1.0, ransac_n=3)
+    with pytest.raises(ValueError):
+        mg.segment_plane(P, 1.0, probability=1.0)
+
+
+def test_select_by_index_invert(mg):
+    rng = np.random.default_rng(3)
+    P = rng.normal(size=(1000, 3))
+    C = rng.integers(0, 256, (1000, 3), dtype=np.uint8)
+    ind = np.sort(rng.choice(1000, 300, replace=False))
+    Q, Cq = mg.select_by_index(P, C, ind, invert=True)
+    keep = np.setdiff1d(np.arange(1000), ind)
+    np.testing.assert_array_equal(Q.cpu().numpy(), P[keep])
+    np.testing.assert_array_equal(Cq.cpu().numpy(), C[keep])
+    Q, _ = mg.select_by_index(P, C, ind)
+    np.testing.assert_array_equal(Q.cpu().numpy(), P[ind])
+    # unsorted with duplicates; nothing listed; everything listed
+    Q, _ = mg.select_by_index(P, None, np.array([5, 999, 5, 0]), invert=True)
+    np.testing.assert_array_equal(Q.cpu().numpy(), P[np.setdiff1d(np.arange(1000), [0, 5, 999])])
+    Q, _ = mg.select_by_index(P, None, np.zeros(0, np.int64), invert=True)
+    np.testing.assert_array_equal(Q.cpu().numpy(), P)
+    Q, Cq = mg.select_by_index(P, C, np.arange(1000), invert=True)
+    assert Q.shape == (0, 3) and Cq.shape == (0, 3)
+    with pytest.raises(IndexError):
+        mg.select_by_index(P, C, np.array([1000]), invert=True)
+
+
+# ---- the processing drop-in ----
+def _write_view(path, n=6000, seed=1):
+    from structured_light_for_3d_model_replication_amd import ply
+    P, _ = po.wall_scene(n, 0.6, rng_seed=seed)
+    C = np.random.default_rng(seed).integers(0, 256, (n, 3), dtype=np.uint8)
+    ply.save_ply_open3d(P, C, path)
+    return P, C
+
+
+def test_remove_background_file(pr, tmp_path, capsys):
+    from structured_light_for_3d_model_replication_amd import ply
+    src, dst = str(tmp_path / "view.ply"), str(tmp_path / "out.ply")
+    P, C = _write_view(src)
+    assert pr.ProcessingLogic.remove_background(src, dst, distance_threshold=10, seed=7) is None
+    _, inl, _ = po.segment_plane(P, 10.0, 3, 1000, seed=7)
+    keep = np.setdiff1d(np.arange(len(P)), inl)
+    Q, Cq = ply.read_ply(dst)
+    np.testing.assert_array_equal(Q, P[keep])
+    np.testing.assert_array_equal(Cq, C[keep])
+    assert capsys.readouterr().out == ("[BG Remove] Processing...\n"
+                                       f"[BG Remove] Original: {len(P)}, Remaining: {len(keep)} pts\n"
+                                       f"[BG Remove] Saved to {dst}\n")
+
+
+def test_remove_background_cloud_in_cloud_out(pr, mg):
+    P, _ = po.wall_scene(6000, 0.6)
+    dev = mg._engine(None).device
+    out = pr.ProcessingLogic.remove_background(pr.Cloud(torch.from_numpy(P).to(dev)), distance_threshold=10,
+                                               return_obj=True, seed=7)
+    assert isinstance(out, pr.Cloud) and out.has_points() and out.colors is None
+    _, inl, _ = po.segment_plane(P, 10.0, 3, 1000, seed=7)
+    assert len(out) == len(P) - len(inl)
+
+
+def test_remove_background_errors(pr, tmp_path):
+    with pytest.raises(FileNotFoundError, match="Input file not found: "):
+        pr.ProcessingLogic.remove_background(str(tmp_path / "missing.ply"))
+    empty = tmp_path / "empty.ply"
+    empty.write_bytes(b"")
+    with pytest.raises(ValueError, match=r"^Point cloud is empty\.$"):
+        pr.ProcessingLogic.remove_background(str(empty))
+    with pytest.raises(ValueError, match=r"^Point cloud is empty\.$"):
+        pr.ProcessingLogic.remove_outliers(str(empty))
+
+
+def test_remove_outliers_is_sor_plus_select(pr, mg, capsys):
+    P, _ = po.wall_scene(6000, 0.6)
+    dev = mg._engine(None).device
+    C = torch.from_numpy(np.random.default_rng(0).integers(0, 256, (6000, 3), dtype=np.uint8)).to(dev)
+    out = pr.ProcessingLogic.remove_outliers(pr.Cloud(torch.from_numpy(P).to(dev), C), nb_neighbors=20,
+                                             std_ratio=2.0, return_obj=True)
+    ind, _ = mg.remove_statistical_outlier(P, 20, 2.0)
+    Q, Cq = mg.select_by_index(P, C, ind)
+    assert torch.equal(out.points, Q) and torch.equal(out.colors, Cq)
+    assert capsys.readouterr().out == f"[Outlier] Processing...\n[Outlier] Keeping: {len(ind)} pts\n"
+
+
+def test_process_folder(pr, tmp_path, capsys):
+    src, dst = tmp_path / "in", tmp_path / "out"
+    src.mkdir()
+    _write_view(str(src / "view_0deg.ply"), 3000, 1)
+    _write_view(str(src / "view_30deg.ply"), 3000, 2)
+    (src / "broken.ply").write_bytes(b"ply\nformat binary_little_endian 1.0\nelement vertex 99\n")
+    assert pr.process_folder(str(src), str(dst), bg_dist=10) == (2, 1)
+    assert sorted(os.listdir(dst)) == ["view_0deg_processed.ply", "view_30deg_processed.ply"]
+    out = capsys.readouterr().out
+    assert "[Task] Processing broken.ply...\n" in out
+    assert "[Task] Error processing broken.ply: Point cloud is empty.\n" in out
+    assert f"[Task] Saved {dst / 'view_0deg_processed.ply'}\n" in out
