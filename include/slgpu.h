@@ -435,6 +435,57 @@ int sl_segment_plane(sl_ctx* ctx, const double* xyz, int64_t n, double distance_
 int sl_index_complement(sl_ctx* ctx, const int64_t* index, int64_t m, int64_t n, int64_t* out_index, int64_t* out_n,
                         void* stream);
 
+/* ---- Poisson meshing (ProcessingLogic.reconstruct_stl / mesh_360, processing.py:185-311) ----
+ * create_from_point_cloud_poisson as Kazhdan's FFT Poisson reconstruction on
+ * a dense periodic grid of R = 2^depth nodes per axis (depth 1..10), node (i,
+ * j, k) at origin + h (i, j, k), linear index (i R + j) R + k.  Open3D's is the
+ * adaptive-octree variant: parity with Open3D is unpinned; csrc/slmesh.inl
+ * states every stage and tests/mesh_oracle.py restates it on the CPU, bit for
+ * bit except the FFT solve, which the Python side runs through torch.fft
+ * (mesh.py).  All pointers are device memory unless noted; every call blocks
+ * on `stream`.
+ *   sl_mesh_splat          trilinear splat of n (< 2^31) points: 64-bit
+ *                          fixed-point (2^-30) integer atomic adds into acc
+ *                          [4][R^3] (weight, then w n_x, w n_y, w n_z), which
+ *                          the caller has zeroed.  origin: host[3].
+ *   sl_mesh_unfix          out[i] = float(double(acc[i]) 2^-30), i < count.
+ *   sl_mesh_divergence     periodic central differences of V [3][R^3] (f32).
+ *   sl_mesh_sample         trilinear value (f64) of an f32 grid at n points.
+ *   sl_ordered_sum         slplane.inl's ordered sum of v[stride i + offset],
+ *                          i < n -> *sum (host).
+ *   sl_orient_normals      orient_normals_towards_camera_location, in place:
+ *                          a normal with n . (location - p) < 0 is negated, a
+ *                          zero normal becomes the unit vector towards
+ *                          location ((0, 0, 1) at the location itself).
+ *                          location: host[3].
+ *   sl_mesh_extract_count  marching tetrahedra, pass 1: emask [R^3] (the
+ *                          crossed edges a node owns), vpos / tpos [R^3] (the
+ *                          first vertex of a node, the first triangle of a
+ *                          cube) and the totals (host); SL_ECAPACITY at 2^31.
+ *   sl_mesh_extract_emit   pass 2, into vertices f64 [n_vertices][3] and
+ *                          triangles int32 [n_triangles][3].
+ *   sl_mesh_remove_vertices  remove_vertices_by_mask: mask u8 [n_vertices]
+ *                          (non-zero: remove); outputs have the inputs'
+ *                          capacity, the new counts -> host. */
+int sl_mesh_splat(sl_ctx* ctx, const double* xyz, const double* normals, int64_t n, int depth, const double* origin,
+                  double h, int64_t* acc, void* stream);
+int sl_mesh_unfix(sl_ctx* ctx, const int64_t* acc, int64_t count, float* out, void* stream);
+int sl_mesh_divergence(sl_ctx* ctx, const float* V, int depth, double h, float* div, void* stream);
+int sl_mesh_sample(sl_ctx* ctx, const float* grid, int depth, const double* origin, double h, const double* xyz,
+                   int64_t n, double* out, void* stream);
+int sl_ordered_sum(sl_ctx* ctx, const double* v, int64_t n, int64_t stride, int64_t offset, double* sum,
+                   void* stream);
+int sl_orient_normals(sl_ctx* ctx, const double* xyz, double* normals, int64_t n, const double* location,
+                      void* stream);
+int sl_mesh_extract_count(sl_ctx* ctx, const float* chi, int depth, double iso, uint8_t* emask, uint32_t* vpos,
+                          uint32_t* tpos, int64_t* n_vertices, int64_t* n_triangles, void* stream);
+int sl_mesh_extract_emit(sl_ctx* ctx, const float* chi, int depth, double iso, const double* origin, double h,
+                         const uint8_t* emask, const uint32_t* vpos, const uint32_t* tpos, int64_t n_vertices,
+                         int64_t n_triangles, double* vertices, int32_t* triangles, void* stream);
+int sl_mesh_remove_vertices(sl_ctx* ctx, const double* vertices, int64_t n_vertices, const int32_t* triangles,
+                            int64_t n_triangles, const uint8_t* mask, double* out_vertices, int32_t* out_triangles,
+                            int64_t* out_n_vertices, int64_t* out_n_triangles, void* stream);
+
 /* Release the scratch buffers the merge entry points keep pooled for `device`
  * (kept otherwise for the process's lifetime, at most 16 GiB per device);
  * the bytes released -> *released_bytes (may be NULL). */

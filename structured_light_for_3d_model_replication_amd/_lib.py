@@ -37,6 +37,8 @@ EXPORTS = ("sl_abi_version", "sl_ctx_create", "sl_ctx_destroy", "sl_ctx_last_err
            "sl_transform_points", "sl_estimate_normals", "sl_icp_point_to_plane", "sl_radius_search", "sl_compute_fpfh",
            "sl_feature_nn", "sl_ransac_feature_matching", "sl_segment_plane", "sl_index_complement", "sl_merge_pool_trim", "sl_calib_products", "sl_gather_unique_id", "sl_gather_init", "sl_gather_counts",
            "sl_gather",
+           "sl_mesh_splat", "sl_mesh_unfix", "sl_mesh_divergence", "sl_mesh_sample", "sl_ordered_sum",
+           "sl_orient_normals", "sl_mesh_extract_count", "sl_mesh_extract_emit", "sl_mesh_remove_vertices",
            "sl_decode_triangulate_batch", "sl_last_error")
 
 _vp = ctypes.c_void_p
@@ -93,6 +95,19 @@ _SIGS = {
                                 ctypes.POINTER(_i32), _vp]),
     "sl_index_complement": (_i32, [_vp, _vp, _i64, _i64, _vp, ctypes.POINTER(_i64), _vp]),
     "sl_merge_pool_trim": (_i32, [_i32, ctypes.POINTER(_i64)]),
+    "sl_mesh_splat": (_i32, [_vp, _vp, _vp, _i64, _i32, ctypes.POINTER(ctypes.c_double), ctypes.c_double, _vp, _vp]),
+    "sl_mesh_unfix": (_i32, [_vp, _vp, _i64, _vp, _vp]),
+    "sl_mesh_divergence": (_i32, [_vp, _vp, _i32, ctypes.c_double, _vp, _vp]),
+    "sl_mesh_sample": (_i32, [_vp, _vp, _i32, ctypes.POINTER(ctypes.c_double), ctypes.c_double, _vp, _i64, _vp,
+                              _vp]),
+    "sl_ordered_sum": (_i32, [_vp, _vp, _i64, _i64, _i64, ctypes.POINTER(ctypes.c_double), _vp]),
+    "sl_orient_normals": (_i32, [_vp, _vp, _vp, _i64, ctypes.POINTER(ctypes.c_double), _vp]),
+    "sl_mesh_extract_count": (_i32, [_vp, _vp, _i32, ctypes.c_double, _vp, _vp, _vp, ctypes.POINTER(_i64),
+                                     ctypes.POINTER(_i64), _vp]),
+    "sl_mesh_extract_emit": (_i32, [_vp, _vp, _i32, ctypes.c_double, ctypes.POINTER(ctypes.c_double),
+                                    ctypes.c_double, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
+    "sl_mesh_remove_vertices": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, ctypes.POINTER(_i64),
+                                       ctypes.POINTER(_i64), _vp]),
     "sl_gather_unique_id": (_i32, [_vp]),
     "sl_gather_init": (_i32, [_vp, _i32, _i32, _vp]),
     "sl_gather_counts": (_i32, [_vp, _i64, _vp, _vp]),

@@ -2112,3 +2112,5 @@ int sl_merge_pool_trim(int device, int64_t* released_bytes) {
 #include "slreg.inl"
 // plane RANSAC of the per-view background removal (uses slreg.inl's draw)
 #include "slplane.inl"
+
+#include "slmesh.inl"

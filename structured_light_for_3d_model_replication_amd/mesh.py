@@ -1,0 +1,322 @@
+"""Poisson meshing on the GPU: the fourth step of the reference's workflow
+(server/processing.py:185-311; ``processing.ProcessingLogic.reconstruct_stl``
+and ``mesh_360`` of this package are the drop-ins built on this module).
+
+``create_from_point_cloud_poisson`` is Kazhdan's FFT Poisson reconstruction on
+a dense periodic grid of R = 2^depth nodes per axis: a trilinear splat of the
+oriented points (64-bit fixed-point integer atomics, so the grids do not depend
+on the order the points arrive in), the divergence of the splatted normals,
+one FFT solve, the iso value as the mean of the field at the points, and
+marching tetrahedra over the six Kuhn tetrahedra of every cube.  Everything
+but the FFT is a HIP kernel of libslgpu.so (csrc/slmesh.inl, which states the
+arithmetic); the FFT is ``torch.fft`` (rocFFT).
+
+Open3D's Poisson is the adaptive-octree variant and is not installed here:
+parity with Open3D is unpinned, and tests/mesh_oracle.py is the CPU restatement
+the tests check against -- bit for bit for every stage except the solve.
+Tensors in and out live on the device; ``origin`` is a NumPy f64 [3].
+"""
+from __future__ import annotations
+
+import ctypes
+import os
+import time
+
+import numpy as np
+import torch
+
+from . import _lib
+from .merge import _engine, _f64, _ptr
+
+_D3 = ctypes.c_double * 3
+MAX_DEPTH = 10  # 2^30 nodes: the scans and the kernels' grid sizes are laid out for it
+
+
+def required_bytes(depth: int, n_points: int) -> int:
+    """Device bytes ``create_from_point_cloud_poisson`` needs at its peak, the
+    splat: four int64 accumulators and the four f32 grids made from them (48
+    bytes a node; every later stage holds less) plus the points, their normals
+    and their samples."""
+    return 48 * (1 << (3 * int(depth))) + 56 * int(n_points)
+
+
+def _check_memory(depth, n, dev, budget_bytes):
+    need = required_bytes(depth, n)
+    if budget_bytes is None:
+        free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
+    else:
+        free = int(budget_bytes)
+    if need > free or depth > MAX_DEPTH:
+        raise MemoryError(f"Poisson reconstruction at depth {depth} needs {need} bytes of device memory; "
+                          f"{free} bytes are available (the largest supported depth is {MAX_DEPTH})")
+
+
+def _depth_of(grid) -> int:
+    R = grid.shape[-1]
+    if grid.dtype != torch.float32 or grid.dim() != 3 or tuple(grid.shape) != (R, R, R) or R < 2 or R & (R - 1):
+        raise ValueError("a grid must be float32 [R, R, R] with R a power of two")
+    return R.bit_length() - 1
+
+
+def _origin(origin):
+    o = np.ascontiguousarray(np.asarray(origin, dtype=np.float64).reshape(3))
+    return _D3(*o.tolist())
+
+
+def _call(eng, name, *args):
+    with eng._lock:
+        _lib.check(getattr(eng._L, name)(eng._ctx, *args, eng._stream(None)), eng._ctx, name)
+
+
+class _Stages:
+    """Milliseconds per stage into ``timings`` (a dict, or None: nothing is measured or synchronised)."""
+
+    def __init__(self, timings, dev):
+        self.timings, self.dev = timings, dev
+        self.mark(None)
+
+    def mark(self, name):
+        if self.timings is None:
+            return
+        torch.cuda.synchronize(self.dev)
+        now = time.perf_counter()
+        if name is not None:
+            self.timings[name] = self.timings.get(name, 0.0) + (now - self.t0) * 1e3
+        self.t0 = now
+
+
+def box(points, depth: int, scale: float = 1.1):
+    """-> (origin f64 [3], h): the cube of side scale * (largest extent) about the points' bounding box."""
+    lo = points.min(0).values.cpu().numpy()
+    hi = points.max(0).values.cpu().numpy()
+    if not (np.isfinite(lo).all() and np.isfinite(hi).all()):
+        raise ValueError("points must be finite")
+    c = (lo + hi) / 2.0
+    L = scale * float((hi - lo).max())
+    if not L > 0.0:
+        L = 1.0
+    if not np.isfinite(L):
+        raise ValueError("scale must be finite")
+    return c - L / 2.0, L / (1 << depth)
+
+
+def ordered_sum(values, stride: int = 1, offset: int = 0, *, device=None) -> float:
+    """The ordered f64 sum (csrc/slplane.inl) of values[offset::stride]."""
+    eng = _engine(device)
+    v = torch.as_tensor(values).to(device=eng.device, dtype=torch.float64).contiguous().reshape(-1)
+    out = ctypes.c_double()
+    _call(eng, "sl_ordered_sum", _ptr(v) if v.numel() else None, v.numel() // stride, stride, offset,
+          ctypes.byref(out))
+    return out.value
+
+
+def get_center(points, *, device=None) -> np.ndarray:
+    """PointCloud.get_center: the mean of the points (ordered sums) -> NumPy f64 [3]."""
+    eng = _engine(device)
+    P = _f64(points, eng.device)
+    if not len(P):
+        return np.zeros(3)
+    return np.array([ordered_sum(P, 3, a, device=eng.device) / float(len(P)) for a in range(3)])
+
+
+def orient_normals_towards_camera_location(points, normals, location=(0.0, 0.0, 0.0), *, device=None):
+    """PointCloud.orient_normals_towards_camera_location -> the oriented normals
+    (a copy): negated where n . (location - p) < 0; a zero normal becomes the
+    unit vector towards the location."""
+    eng = _engine(device)
+    P = _f64(points, eng.device)
+    N = _f64(normals, eng.device).clone()
+    if N.shape != P.shape:
+        raise ValueError("a normal per point is needed")
+    _call(eng, "sl_orient_normals", _ptr(P), _ptr(N), P.shape[0], _origin(location))
+    return N
+
+
+def sample(grid, points, origin, h, *, device=None) -> torch.Tensor:
+    """Trilinear value (f64) of a float32 [R, R, R] grid at every point."""
+    eng = _engine(device)
+    G = torch.as_tensor(grid).to(eng.device).contiguous()
+    depth = _depth_of(G)
+    P = _f64(points, eng.device)
+    out = torch.empty(max(len(P), 1), dtype=torch.float64, device=eng.device)
+    _call(eng, "sl_mesh_sample", _ptr(G), depth, _origin(origin), float(h), _ptr(P), P.shape[0], _ptr(out))
+    return out[: len(P)]
+
+
+def vertex_density(W, vertices, origin, h, *, device=None) -> torch.Tensor:
+    """The density of every vertex: the splatted weight W at its position."""
+    return sample(W, vertices, origin, h, device=device)
+
+
+def solve(div, h) -> torch.Tensor:
+    """chi = irfftn(rfftn(div) / lambda), lambda the 7-point Laplacian's eigenvalues, chi^(0) = 0 (float32)."""
+    R = div.shape[0]
+    c = torch.from_numpy((2.0 * np.cos(2.0 * np.pi * np.arange(R) / R) - 2.0).astype(np.float32)).to(div.device)
+    F = torch.fft.rfftn(div)
+    lam = (c[:, None, None] + c[None, :, None]) + c[None, None, : R // 2 + 1]
+    lam /= float(np.float32(h * h))
+    lam[0, 0, 0] = 1.0
+    F /= lam
+    del lam
+    F[0, 0, 0] = 0.0
+    return torch.fft.irfftn(F, s=tuple(div.shape)).contiguous()
+
+
+def poisson_field(points, normals, depth: int, scale: float = 1.1, *, keep: bool = False, budget_bytes=None,
+                  timings=None, device=None) -> dict:
+    """Splat, divergence, solve and iso value -> {"chi", "W" (float32 [R, R, R]),
+    "iso", "origin", "h"}; with ``keep`` also "V" (float32 [3, R, R, R]) and
+    "div".  ``budget_bytes`` replaces the device's free memory in the check
+    that raises MemoryError before anything is allocated; ``timings`` (a dict)
+    receives the milliseconds of each stage."""
+    eng = _engine(device)
+    P = _f64(points, eng.device)
+    N = _f64(normals, eng.device)
+    if N.shape != P.shape:
+        raise ValueError("a normal per point is needed")
+    n = P.shape[0]
+    if n == 0:
+        raise ValueError("no points")
+    depth = int(depth)
+    if depth < 1:
+        raise ValueError("depth must be at least 1")
+    _check_memory(depth, n, eng.device, budget_bytes)
+    R = 1 << depth
+    st = _Stages(timings, eng.device)
+    origin, h = box(P, depth, scale)
+    o = _origin(origin)
+    acc = torch.zeros((4, R, R, R), dtype=torch.int64, device=eng.device)
+    _call(eng, "sl_mesh_splat", _ptr(P), _ptr(N), n, depth, o, h, _ptr(acc))
+    G = torch.empty((4, R, R, R), dtype=torch.float32, device=eng.device)
+    _call(eng, "sl_mesh_unfix", _ptr(acc), acc.numel(), _ptr(G))
+    del acc  # the accumulators are gone before the FFT
+    st.mark("splat")
+    W = G[0].clone()
+    V = G[1:]
+    div = torch.empty((R, R, R), dtype=torch.float32, device=eng.device)
+    _call(eng, "sl_mesh_divergence", _ptr(V), depth, h, _ptr(div))
+    out = {"W": W, "origin": origin, "h": h}
+    if keep:
+        out["V"] = V.clone()
+        out["div"] = div.clone()
+    del G, V
+    st.mark("divergence")
+    chi = solve(div, h)
+    del div
+    st.mark("solve")
+    out["chi"] = chi
+    out["iso"] = iso_value(chi, P, origin, h, device=eng.device)
+    st.mark("iso")
+    return out
+
+
+def iso_value(chi, points, origin, h, *, device=None) -> float:
+    """The mean of chi at the points (ordered sum)."""
+    s = sample(chi, points, origin, h, device=device)
+    return ordered_sum(s, device=s.device) / float(len(s))
+
+
+def extract_isosurface(chi, iso: float, origin, h, *, device=None):
+    """Marching tetrahedra -> (vertices f64 [V, 3], triangles int32 [T, 3]);
+    triangles are wound so that the normal points to the chi > iso side."""
+    eng = _engine(device)
+    chi = torch.as_tensor(chi).to(eng.device).contiguous()
+    depth = _depth_of(chi)
+    n3 = chi.numel()
+    o = _origin(origin)
+    emask = torch.empty(n3, dtype=torch.uint8, device=eng.device)
+    vpos = torch.empty(n3, dtype=torch.int32, device=eng.device)
+    tpos = torch.empty(n3, dtype=torch.int32, device=eng.device)
+    nv, nt = ctypes.c_int64(), ctypes.c_int64()
+    _call(eng, "sl_mesh_extract_count", _ptr(chi), depth, float(iso), _ptr(emask), _ptr(vpos), _ptr(tpos),
+          ctypes.byref(nv), ctypes.byref(nt))
+    verts = torch.empty((max(nv.value, 1), 3), dtype=torch.float64, device=eng.device)
+    tris = torch.empty((max(nt.value, 1), 3), dtype=torch.int32, device=eng.device)
+    _call(eng, "sl_mesh_extract_emit", _ptr(chi), depth, float(iso), o, float(h), _ptr(emask), _ptr(vpos),
+          _ptr(tpos), nv.value, nt.value, _ptr(verts), _ptr(tris))
+    return verts[: nv.value], tris[: nt.value]
+
+
+def remove_vertices_by_mask(vertices, triangles, mask, *, device=None):
+    """TriangleMesh.remove_vertices_by_mask -> (vertices, triangles): the masked
+    vertices and every triangle that has one go; the rest keep their order."""
+    eng = _engine(device)
+    Vx = _f64(vertices, eng.device)
+    T = torch.as_tensor(triangles).to(device=eng.device, dtype=torch.int32).contiguous().reshape(-1, 3)
+    M = torch.as_tensor(mask).to(device=eng.device).reshape(-1).ne(0).to(torch.uint8).contiguous()
+    if len(M) != len(Vx):
+        raise ValueError("a mask entry per vertex is needed")
+    ov = torch.empty((max(len(Vx), 1), 3), dtype=torch.float64, device=eng.device)
+    ot = torch.empty((max(len(T), 1), 3), dtype=torch.int32, device=eng.device)
+    nv, nt = ctypes.c_int64(), ctypes.c_int64()
+    _call(eng, "sl_mesh_remove_vertices", _ptr(Vx), len(Vx), _ptr(T), len(T), _ptr(M), _ptr(ov), _ptr(ot),
+          ctypes.byref(nv), ctypes.byref(nt))
+    return ov[: nv.value], ot[: nt.value]
+
+
+def quantile(values, q: float) -> float:
+    """numpy.quantile(values, q) (linear), the sort on the device."""
+    s = torch.sort(values.reshape(-1)).values
+    pos = q * (len(s) - 1)
+    lo = int(np.floor(pos))
+    hi = min(lo + 1, len(s) - 1)
+    a, b = (float(x) for x in s[[lo, hi]].cpu().numpy())
+    t = pos - lo
+    d = b - a
+    return b - d * (1.0 - t) if t >= 0.5 else a + d * t
+
+
+def trim_by_density(vertices, triangles, densities, q: float, *, device=None):
+    """remove_vertices_by_mask(densities < quantile(densities, q))."""
+    return remove_vertices_by_mask(vertices, triangles, densities < quantile(densities, q), device=device)
+
+
+def create_from_point_cloud_poisson(points, normals, depth: int = 8, scale: float = 1.1, *, budget_bytes=None,
+                                    timings=None, device=None):
+    """TriangleMesh.create_from_point_cloud_poisson -> (vertices f64 [V, 3],
+    triangles int32 [T, 3], densities f64 [V]) on the device."""
+    f = poisson_field(points, normals, depth, scale, budget_bytes=budget_bytes, timings=timings, device=device)
+    chi = f.pop("chi")
+    st = _Stages(timings, chi.device)
+    verts, tris = extract_isosurface(chi, f["iso"], f["origin"], f["h"], device=chi.device)
+    del chi
+    st.mark("extract")
+    dens = vertex_density(f["W"], verts, f["origin"], f["h"], device=verts.device)
+    st.mark("density")
+    return verts, tris, dens
+
+
+def _host(a, dtype):
+    if isinstance(a, torch.Tensor):
+        a = a.cpu().numpy()
+    return np.ascontiguousarray(np.asarray(a, dtype=dtype)).reshape(-1, 3)
+
+
+_STL_REC = np.dtype([("normal", "<f4", 3), ("v", "<f4", (3, 3)), ("attr", "<u2")])
+
+
+def write_triangle_mesh(path, vertices, triangles) -> None:
+    """o3d.io.write_triangle_mesh for ``.stl``: binary STL (80-byte header, the
+    count, per triangle the unit normal, three vertices and a zero attribute,
+    float32).  Normals are taken in f64 from the f64 vertices; a zero-area
+    triangle gets a zero normal."""
+    if os.path.splitext(str(path))[1].lower() != ".stl":
+        raise ValueError(f"cannot write {path}: only .stl is supported")
+    P = _host(vertices, np.float64)
+    T = _host(triangles, np.int64)
+    if len(T) and (T.min() < 0 or T.max() >= len(P)):
+        raise IndexError("triangle index out of range")
+    p0, p1, p2 = P[T[:, 0]], P[T[:, 1]], P[T[:, 2]]
+    e1, e2 = p1 - p0, p2 - p0
+    n = np.stack([e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1], e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2],
+                  e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]], 1)
+    ln = np.sqrt((n[:, 0] * n[:, 0] + n[:, 1] * n[:, 1]) + n[:, 2] * n[:, 2])
+    with np.errstate(invalid="ignore", divide="ignore"):
+        n = np.where((ln == 0.0)[:, None], 0.0, n / ln[:, None])
+    rec = np.zeros(len(T), dtype=_STL_REC)
+    rec["normal"] = n
+    rec["v"][:, 0], rec["v"][:, 1], rec["v"][:, 2] = p0, p1, p2
+    with open(path, "wb") as f:
+        f.write(b"\0" * 80)
+        f.write(np.uint32(len(T)).tobytes())
+        rec.tofile(f)

@@ -13,7 +13,17 @@ errors, and runs them on the GPU through ``merge`` (libslgpu.so):
   ``merge.select_by_index``.
 * ``preprocess_point_cloud``, ``execute_global_registration`` and
   ``merge_pro_360`` delegate to ``merge``.
-* ``reconstruct_stl`` and ``mesh_360`` (Poisson meshing) are NOT provided.
+* ``reconstruct_stl`` (:185-249) and ``mesh_360`` (:252-311) -> ``mesh.
+  create_from_point_cloud_poisson`` (FFT Poisson reconstruction on a dense
+  grid and marching tetrahedra, csrc/slmesh.inl), the density trim and a
+  binary STL.  Open3D's Poisson is the adaptive-octree variant: the surfaces
+  agree in kind, not vertex for vertex.  Deviations: normals that have to be
+  estimated are oriented towards the scanner's camera at the origin
+  (``orient_normals_consistent_tangent_plane`` is not provided), so
+  ``mesh_360``'s ``"tangent"`` mode takes the reference's own fall-back to the
+  radial orientation; ``mode="surface"`` (ball pivoting) raises
+  NotImplementedError; only ``.stl`` can be written; a depth whose grids do
+  not fit the device raises MemoryError (depth 10 is the largest).
 
 Without Open3D, "a point cloud object" is a ``Cloud(points, colors)`` of
 device tensors (f64 [N, 3], BGR u8 [N, 3] or None).  It is accepted wherever
@@ -39,7 +49,7 @@ import os
 import numpy as np
 import torch
 
-from . import merge, ply
+from . import merge, mesh, ply
 
 
 class Cloud:
@@ -124,6 +134,83 @@ class ProcessingLogic:
     @staticmethod
     def merge_pro_360(input_folder, output_path, voxel_size=0.02):
         merge.merge_pro_360(input_folder, output_path, voxel_size)
+
+    @staticmethod
+    def _load_for_meshing(input_path):
+        """-> (points, normals | None) on the device (a file that cannot be parsed: an empty cloud)."""
+        try:
+            P, _ = ply.read_ply(input_path)
+            N = ply.read_normals(input_path)
+        except (ValueError, KeyError, IndexError):
+            P, N = np.zeros((0, 3)), None
+        if len(P) == 0:
+            raise ValueError("Point cloud is empty.")
+        dev = merge._engine(None).device
+        to = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)  # noqa: E731
+        return to(P), (None if N is None else to(N))
+
+    @staticmethod
+    def reconstruct_stl(input_path, output_path, mode="watertight", params=None, *, budget_bytes=None):
+        if not os.path.exists(input_path):
+            raise FileNotFoundError(f"Input file not found: {input_path}")
+        params = {} if params is None else params
+        print(f"[Recon] Loading {input_path}...")
+        P, N = ProcessingLogic._load_for_meshing(input_path)
+        if N is None:
+            print("[Recon] Estimating normals...")
+            N = merge.estimate_normals(P, radius=10, max_nn=30, device=P.device)
+            # deviation: towards the camera at the origin, not orient_normals_consistent_tangent_plane(100)
+            N = mesh.orient_normals_towards_camera_location(P, N, (0.0, 0.0, 0.0), device=P.device)
+        if mode == "watertight":
+            depth = int(params.get("depth", 10))
+            if depth > 16:
+                raise ValueError(f"Depth {depth} is too high! Maximum recommended is 12-14. >16 will freeze your PC.")
+            print(f"[Recon] Poisson Reconstruction (depth={depth})...")
+            V, T, densities = mesh.create_from_point_cloud_poisson(P, N, depth=depth, budget_bytes=budget_bytes,
+                                                                   device=P.device)
+            if len(V):
+                V, T = mesh.trim_by_density(V, T, densities, 0.02, device=P.device)
+        elif mode == "surface":
+            raise NotImplementedError("mode 'surface' (ball pivoting) is not provided; use mode='watertight'")
+        else:
+            raise ValueError(f"Unknown mode: {mode}")
+        if len(V) == 0:
+            raise ValueError("Generated mesh is empty.")
+        print("[Recon] Computing normals and saving...")
+        mesh.write_triangle_mesh(output_path, V, T)
+        print(f"[Recon] Saved STL to {output_path}")
+
+    @staticmethod
+    def mesh_360(input_path, output_path, depth=10, density_trim=0.01, orientation_mode="tangent", *,
+                 budget_bytes=None):
+        if not os.path.exists(input_path):
+            raise FileNotFoundError(f"Input file not found: {input_path}")
+        print(f"[360 Mesh] Loading {input_path}...")
+        P, _ = ProcessingLogic._load_for_meshing(input_path)
+        print("[360 Mesh] Estimating normals...")
+        N = merge.estimate_normals(P, radius=0.1, max_nn=30, device=P.device)
+        print(f"[360 Mesh] Re-orienting normals (Mode: {orientation_mode})...")
+
+        def radial():  # towards the centre, then negated: outwards
+            return -mesh.orient_normals_towards_camera_location(P, N, mesh.get_center(P, device=P.device),
+                                                                device=P.device)
+        if orientation_mode == "radial":
+            N = radial()
+            print("[360 Mesh] Radial orientation applied (Outwards).")
+        else:  # "tangent": orient_normals_consistent_tangent_plane is not provided -> the reference's fall-back
+            print("[360 Mesh] Warning: Tangent plane failed (not provided). Fallback to radial.")
+            N = radial()
+        print(f"[360 Mesh] Poisson Reconstruction (depth={depth})...")
+        V, T, densities = mesh.create_from_point_cloud_poisson(P, N, depth=int(depth), budget_bytes=budget_bytes,
+                                                               device=P.device)
+        if density_trim > 0.0:
+            print(f"[360 Mesh] Trimming low density vertices (threshold={density_trim})...")
+            if len(V):
+                V, T = mesh.trim_by_density(V, T, densities, density_trim, device=P.device)
+        else:
+            print("[360 Mesh] Density trim is 0.0 -> Keeping watertight result.")
+        mesh.write_triangle_mesh(output_path, V, T)
+        print(f"[360 Mesh] Saved to {output_path}")
 
 
 def process_folder(in_dir, out_dir, *, bg_dist=50, bg_ransac_n=3, bg_iterations=1000, nb_neighbors=20,
