@@ -269,7 +269,8 @@ def feature_nn(A, B):
     B = np.asarray(B, dtype=np.float64)
     out = np.empty(len(A), dtype=np.int64)
     for i in range(len(A)):
-        d = feature_dist2(A[i], B)
+        with np.errstate(invalid="ignore"):  # (inf - inf in a row that holds inf)
+            d = feature_dist2(A[i], B)
         d = np.where(np.isnan(d), np.inf, d)
         k = int(np.argmin(d)) if len(d) else -1  # argmin: first of equal minima
         out[i] = k if k >= 0 and d[k] < np.inf else -1
@@ -495,10 +496,13 @@ def validate(source, target, M, max_dist, tree):
 
 
 def ransac_based_on_feature_matching(source, target, fs, ft, max_dist, seed=0, mutual_filter=True,
-                                     edge_sim=0.9, max_iteration=100000, confidence=0.999):
+                                     edge_sim=0.9, max_iteration=100000, confidence=0.999, trace=None):
     """registration_ransac_based_on_feature_matching (processing.py:98-111)
     -> dict(transformation, fitness, inlier_rmse, iterations, validations,
-    corres)."""
+    corres).  ``trace``: a list that receives one (flag, (c0, c1, c2)) per
+    iteration -- flag 0: the edge-length check failed, 1: the distance check
+    failed, 2: the hypothesis was validated; c*: the drawn correspondence
+    indices (the results are the same with and without it)."""
     from scipy.spatial import cKDTree
     S = np.asarray(source, dtype=np.float64)
     Tg = np.asarray(target, dtype=np.float64)
@@ -517,13 +521,20 @@ def ransac_based_on_feature_matching(source, target, fs, ft, max_dist, seed=0, m
     thr2 = max_dist * max_dist
     log_conf = math.log(1.0 - confidence) if confidence < 1.0 else -math.inf
     while it < max_iteration and it < est_k:
-        c = [cl[draw(seed, 3 * it + j, nc)] for j in range(3)]
+        drawn = tuple(draw(seed, 3 * it + j, nc) for j in range(3))
+        c = [cl[k] for k in drawn]
         it += 1
         if not edge_length_ok(Sl, Tl, c, edge_sim):
+            if trace is not None:
+                trace.append((0, drawn))
             continue
         M = umeyama3([Sl[x[0]] for x in c], [Tl[x[1]] for x in c])
         if not distance_ok(Sl, Tl, c, M, max_dist):
+            if trace is not None:
+                trace.append((1, drawn))
             continue
+        if trace is not None:
+            trace.append((2, drawn))
         vals += 1
         fit, rmse, Q = validate(S, Tg, M, max_dist, tree)
         if fit > best["fitness"] or (fit == best["fitness"] and rmse < best["inlier_rmse"]):
