@@ -486,6 +486,40 @@ int sl_mesh_remove_vertices(sl_ctx* ctx, const double* vertices, int64_t n_verti
                             int64_t n_triangles, const uint8_t* mask, double* out_vertices, int32_t* out_triangles,
                             int64_t* out_n_vertices, int64_t* out_n_triangles, void* stream);
 
+/* ---- consistent tangent-plane normal orientation (processing.py:201, :282) ----
+ * orient_normals_consistent_tangent_plane restated on the kNN graph alone
+ * (csrc/slorient.inl; tests/orient_oracle.py is the CPU restatement, bit for
+ * bit).  Open3D adds Delaunay-EMST edges, which connect the graph; this does
+ * not, so every connected component is oriented on its own, and parity with
+ * Open3D is unpinned.  normals [n][3] (device f64) are oriented IN PLACE; each
+ * comes out exactly +n or -n.
+ *   graph   idx [n][k], cnt [n] as sl_radius_search writes them.  Slot s = i k +
+ *           j names the entry (i, idx[i][j]); every slot with j < cnt[i] and
+ *           idx[i][j] != i is an undirected edge candidate.  n k < 2^32.
+ *   weight  dot = (nx mx + ny my) + nz mz (f64, uncontracted); w = 1 - |dot|
+ *           where that is > 0, else 0.
+ *   order   (w, slot): strict and total, so the minimum spanning forest is
+ *           unique as a set of slots.
+ *   parity  an edge flips iff dot < 0.
+ *   root    per component the point of largest z (lowest index on ties); the
+ *           component is negated iff the root's nz < 0; every other point's
+ *           sign is the XOR of the flipping edges on its tree path to the root.
+ * tree_slots (device, [n], or NULL) receives the forest's slots, one per point
+ * that is not the last of its component to be merged, in ascending order of
+ * that point (the same in every run; sort it to compare sets); their number ->
+ * *n_tree and the number of components -> *n_components (host; n_tree +
+ * n_components = n).  n == 0 succeeds and writes nothing.  SL_EINVAL: k < 1,
+ * NULL arguments, n >= 2^31, n k >= 2^32.  Boruvka rounds with parity-carrying
+ * union-find; the host reads a counter per round and a flag per pointer jump,
+ * both bounded by ceil(log2 n) + 2 (SL_EHIP "internal error" beyond, never a
+ * spin).  Scratch: 8 n k bytes (a key per slot) + 30 n.  Blocking on `stream`.
+ * sl_orient_normals_mst_stats: the calling thread's last call's rounds and the
+ * jump launches of each (jumps[capacity], zero-filled) -- a measurement aid. */
+int sl_orient_normals_mst(sl_ctx* ctx, const double* xyz, double* normals, int64_t n, const int32_t* idx,
+                          const int32_t* cnt, int k, uint32_t* tree_slots, int64_t* n_tree, int64_t* n_components,
+                          void* stream);
+int sl_orient_normals_mst_stats(int* rounds, int* jumps, int capacity);
+
 /* Release the scratch buffers the merge entry points keep pooled for `device`
  * (kept otherwise for the process's lifetime, at most 16 GiB per device);
  * the bytes released -> *released_bytes (may be NULL). */

@@ -2114,3 +2114,5 @@ int sl_merge_pool_trim(int device, int64_t* released_bytes) {
 #include "slplane.inl"
 
 #include "slmesh.inl"
+// consistent tangent-plane normal orientation (kNN-graph MST) for the meshing drop-ins
+#include "slorient.inl"

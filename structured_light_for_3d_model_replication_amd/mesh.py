@@ -11,6 +11,12 @@ marching tetrahedra over the six Kuhn tetrahedra of every cube.  Everything
 but the FFT is a HIP kernel of libslgpu.so (csrc/slmesh.inl, which states the
 arithmetic); the FFT is ``torch.fft`` (rocFFT).
 
+``orient_normals_consistent_tangent_plane`` orients estimated normals before
+that: the reference's call restated on the kNN graph alone (a minimum spanning
+forest over 1 - |ni . nj| by Boruvka rounds, csrc/slorient.inl, checked bit for
+bit against tests/orient_oracle.py); the drop-ins use it when asked to
+(``tangent_planes=k``).
+
 Open3D's Poisson is the adaptive-octree variant and is not installed here:
 parity with Open3D is unpinned, and tests/mesh_oracle.py is the CPU restatement
 the tests check against -- bit for bit for every stage except the solve.
@@ -130,6 +136,55 @@ def orient_normals_towards_camera_location(points, normals, location=(0.0, 0.0, 
         raise ValueError("a normal per point is needed")
     _call(eng, "sl_orient_normals", _ptr(P), _ptr(N), P.shape[0], _origin(location))
     return N
+
+
+def orient_normals_mst(points, normals, idx, cnt, *, device=None):
+    """sl_orient_normals_mst over a given graph (``idx`` int32 [N, k], ``cnt``
+    int32 [N], as ``merge.radius_search`` returns them) -> (the oriented normals
+    (a copy), {"components", "tree_slots" (int64, ascending), "rounds", "jumps"})."""
+    eng = _engine(device)
+    P = _f64(points, eng.device)
+    N = _f64(normals, eng.device).clone()
+    if N.shape != P.shape:
+        raise ValueError("a normal per point is needed")
+    n = P.shape[0]
+    I = torch.as_tensor(idx).to(device=eng.device, dtype=torch.int32).contiguous()
+    C = torch.as_tensor(cnt).to(device=eng.device, dtype=torch.int32).contiguous().reshape(-1)
+    if I.dim() != 2 or I.shape[0] != n or C.shape[0] != n:
+        raise ValueError("the graph needs a row of neighbours and a count per point")
+    k = I.shape[1]
+    tree = torch.empty(max(n, 1), dtype=torch.int32, device=eng.device)  # slots are uint32
+    nt, nc = ctypes.c_int64(), ctypes.c_int64()
+    _call(eng, "sl_orient_normals_mst", _ptr(P) if n else None, _ptr(N) if n else None, n,
+          _ptr(I) if n and k else None, _ptr(C) if n else None, k, _ptr(tree), ctypes.byref(nt), ctypes.byref(nc))
+    rounds, jumps = ctypes.c_int(), (ctypes.c_int * 40)()
+    with eng._lock:
+        _lib.check(eng._L.sl_orient_normals_mst_stats(ctypes.byref(rounds), jumps, 40), None,
+                   "sl_orient_normals_mst_stats")
+    slots = torch.sort(tree[: nt.value].to(torch.int64) & 0xFFFFFFFF).values
+    return N, {"components": nc.value, "tree_slots": slots, "rounds": rounds.value,
+               "jumps": list(jumps[: rounds.value])}
+
+
+def orient_normals_consistent_tangent_plane(points, normals, k: int = 100, *, radius, device=None, info=False):
+    """PointCloud.orient_normals_consistent_tangent_plane(k) -> the oriented
+    normals f64 [N, 3] on the device (a copy); with ``info`` also {"components",
+    "tree_slots", ...}.  Restated on the kNN graph alone (csrc/slorient.inl
+    states the rules): the graph is ``merge.radius_search(points, radius, k)``,
+    edges weigh 1 - |ni . nj| and are ordered by (weight, slot), the minimum
+    spanning forest propagates the signs, and every connected component is
+    rooted at its highest point, whose normal is made to point up.  Open3D adds
+    Delaunay-EMST edges, which connect the graph; here a graph of more than one
+    component is oriented component by component ("components" tells)."""
+    eng = _engine(device)
+    P = _f64(points, eng.device)
+    N = _f64(normals, eng.device)
+    if N.shape != P.shape:
+        raise ValueError("a normal per point is needed")
+    from . import merge
+    idx, _, cnt = merge.radius_search(P, radius, int(k), device=eng.device)
+    out, inf = orient_normals_mst(P, N, idx, cnt, device=eng.device)
+    return (out, inf) if info else out
 
 
 def sample(grid, points, origin, h, *, device=None) -> torch.Tensor:

@@ -17,13 +17,17 @@ errors, and runs them on the GPU through ``merge`` (libslgpu.so):
   create_from_point_cloud_poisson`` (FFT Poisson reconstruction on a dense
   grid and marching tetrahedra, csrc/slmesh.inl), the density trim and a
   binary STL.  Open3D's Poisson is the adaptive-octree variant: the surfaces
-  agree in kind, not vertex for vertex.  Deviations: normals that have to be
-  estimated are oriented towards the scanner's camera at the origin
-  (``orient_normals_consistent_tangent_plane`` is not provided), so
-  ``mesh_360``'s ``"tangent"`` mode takes the reference's own fall-back to the
-  radial orientation; ``mode="surface"`` (ball pivoting) raises
-  NotImplementedError; only ``.stl`` can be written; a depth whose grids do
-  not fit the device raises MemoryError (depth 10 is the largest).
+  agree in kind, not vertex for vertex.  Deviations: by default normals that
+  have to be estimated are oriented towards the scanner's camera at the
+  origin, and ``mesh_360``'s ``"tangent"`` mode takes the reference's own
+  fall-back to the radial orientation.  One extra keyword-only argument,
+  ``tangent_planes=k`` (the reference's value is 100), switches both to
+  ``mesh.orient_normals_consistent_tangent_plane(k)`` -- the reference's call,
+  restated on the kNN graph of the radius the function estimates normals with
+  (csrc/slorient.inl); it stays opt-in until it has run on real scans.
+  ``mode="surface"`` (ball pivoting) raises NotImplementedError; only ``.stl``
+  can be written; a depth whose grids do not fit the device raises
+  MemoryError (depth 10 is the largest).
 
 Without Open3D, "a point cloud object" is a ``Cloud(points, colors)`` of
 device tensors (f64 [N, 3], BGR u8 [N, 3] or None).  It is accepted wherever
@@ -150,7 +154,8 @@ class ProcessingLogic:
         return to(P), (None if N is None else to(N))
 
     @staticmethod
-    def reconstruct_stl(input_path, output_path, mode="watertight", params=None, *, budget_bytes=None):
+    def reconstruct_stl(input_path, output_path, mode="watertight", params=None, *, budget_bytes=None,
+                        tangent_planes=None):
         if not os.path.exists(input_path):
             raise FileNotFoundError(f"Input file not found: {input_path}")
         params = {} if params is None else params
@@ -159,8 +164,12 @@ class ProcessingLogic:
         if N is None:
             print("[Recon] Estimating normals...")
             N = merge.estimate_normals(P, radius=10, max_nn=30, device=P.device)
-            # deviation: towards the camera at the origin, not orient_normals_consistent_tangent_plane(100)
-            N = mesh.orient_normals_towards_camera_location(P, N, (0.0, 0.0, 0.0), device=P.device)
+            if tangent_planes is None:
+                # deviation: towards the camera at the origin, not orient_normals_consistent_tangent_plane(100)
+                N = mesh.orient_normals_towards_camera_location(P, N, (0.0, 0.0, 0.0), device=P.device)
+            else:  # a graph that is not connected: every component by its own root
+                N = mesh.orient_normals_consistent_tangent_plane(P, N, int(tangent_planes), radius=10,
+                                                                 device=P.device)
         if mode == "watertight":
             depth = int(params.get("depth", 10))
             if depth > 16:
@@ -182,7 +191,7 @@ class ProcessingLogic:
 
     @staticmethod
     def mesh_360(input_path, output_path, depth=10, density_trim=0.01, orientation_mode="tangent", *,
-                 budget_bytes=None):
+                 budget_bytes=None, tangent_planes=None):
         if not os.path.exists(input_path):
             raise FileNotFoundError(f"Input file not found: {input_path}")
         print(f"[360 Mesh] Loading {input_path}...")
@@ -197,9 +206,19 @@ class ProcessingLogic:
         if orientation_mode == "radial":
             N = radial()
             print("[360 Mesh] Radial orientation applied (Outwards).")
-        else:  # "tangent": orient_normals_consistent_tangent_plane is not provided -> the reference's fall-back
+        elif tangent_planes is None:  # "tangent" without the opt-in -> the reference's fall-back
             print("[360 Mesh] Warning: Tangent plane failed (not provided). Fallback to radial.")
             N = radial()
+        else:
+            No, info = mesh.orient_normals_consistent_tangent_plane(P, N, int(tangent_planes), radius=0.1,
+                                                                    device=P.device, info=True)
+            if info["components"] == 1:
+                N = No
+                print("[360 Mesh] Consistent tangent plane orientation applied.")
+            else:  # the reference's failure path (there: an exception of Open3D's)
+                print(f"[360 Mesh] Warning: Tangent plane failed (graph has {info['components']} components). "
+                      "Fallback to radial.")
+                N = radial()
         print(f"[360 Mesh] Poisson Reconstruction (depth={depth})...")
         V, T, densities = mesh.create_from_point_cloud_poisson(P, N, depth=int(depth), budget_bytes=budget_bytes,
                                                                device=P.device)
