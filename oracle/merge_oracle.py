@@ -68,16 +68,19 @@ def voxel_down_sample(points, colors, voxel_size):
     return out, oc
 
 
-def knn_mean_distances(points, nb_neighbors, chunk=512):
+def knn_mean_distances(points, nb_neighbors, chunk=512, queries=None):
     """Mean of the square roots of the nb_neighbors smallest squared distances
     (the point itself included), accumulated in ascending order.  Brute force:
-    small clouds only."""
+    small clouds only.  With queries (an index array): the means of those
+    points only, each against the whole cloud (a larger cloud stays
+    affordable when only a few of its points are checked)."""
     P = np.asarray(points, dtype=np.float64)
-    n = len(P)
-    kk = min(nb_neighbors, n)
+    kk = min(nb_neighbors, len(P))
+    Q = P if queries is None else P[np.asarray(queries, dtype=np.int64)]
+    n = len(Q)
     avg = np.empty(n)
     for a in range(0, n, chunk):
-        q = P[a:a + chunk]
+        q = Q[a:a + chunk]
         d0 = q[:, None, 0] - P[None, :, 0]
         d1 = q[:, None, 1] - P[None, :, 1]
         d2 = q[:, None, 2] - P[None, :, 2]

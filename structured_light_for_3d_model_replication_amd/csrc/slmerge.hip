@@ -1742,8 +1742,8 @@ int sl_statistical_outliers(sl_ctx* c, const double* xyz, int64_t n, int nb_neig
     unsigned h[2 * kMaxLevels];
     MTRY(c, hipMemcpyAsync(h, st.p, sizeof(h), hipMemcpyDeviceToHost, s));
     MTRY(c, hipStreamSynchronize(s));
-    fprintf(stderr, "[slmerge] n=%lld h0=%g l0=%d levels=%d m(l0)=%lld fast-done=%u slow-done:", (long long)n, h0,
-            py.l0, py.levels, (long long)py.m[py.l0], h[py.l0]);
+    fprintf(stderr, "[slmerge] n=%lld h0=%g l0=%d levels=%d sort_bits=%d m(l0)=%lld fast-done=%u slow-done:",
+            (long long)n, h0, py.l0, py.levels, 3 * bits_axis, (long long)py.m[py.l0], h[py.l0]);
     for (int l = 0; l < py.levels; ++l) fprintf(stderr, " %u", h[kMaxLevels + l]);
     fprintf(stderr, "\n");
   }
