@@ -425,11 +425,6 @@ __global__ __launch_bounds__(kT) void k_gather_sorted(const double* xyz, const u
   for (int k = 0; k < 3; ++k) sxyz[3 * t + k] = xyz[3 * i + k];
 }
 
-// The 27 neighbour cells (-1: empty or outside) of every occupied cell of a
-// level, (dx, dy, dz) in -1..1 nesting order.
-__global__ __launch_bounds__(kT) void k_cell_neighbours(const uint64_t* ukeys, int64_t m, int64_t nx, int64_t ny,
-                                                        int64_t nz, int32_t* nbr);
-
 __device__ __forceinline__ uint64_t compact3(uint64_t x) {
   x &= 0x1249249249249249ull;
   x = (x | (x >> 2)) & 0x10c30c30c30c30c3ull;
@@ -440,20 +435,27 @@ __device__ __forceinline__ uint64_t compact3(uint64_t x) {
   return x;
 }
 
+// The 27 neighbour cells (-1: empty or outside) of every occupied cell,
+// (dx, dy, dz) in -1..1 nesting order.  Keys: Morton codes (a pyramid level)
+// or linear, (ix * ny + iy) * nz + iz (a search grid).
+template <bool kMorton>
 __global__ __launch_bounds__(kT) void k_cell_neighbours(const uint64_t* ukeys, int64_t m, int64_t nx, int64_t ny,
                                                         int64_t nz, int32_t* nbr) {
   const int64_t c = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
   if (c >= m) return;
   const uint64_t key = ukeys[c];
-  const int64_t x = static_cast<int64_t>(compact3(key)), y = static_cast<int64_t>(compact3(key >> 1)),
-                z = static_cast<int64_t>(compact3(key >> 2));
+  const int64_t lin = static_cast<int64_t>(key);
+  const int64_t x = kMorton ? static_cast<int64_t>(compact3(key)) : lin / (ny * nz),
+                y = kMorton ? static_cast<int64_t>(compact3(key >> 1)) : (lin / nz) % ny,
+                z = kMorton ? static_cast<int64_t>(compact3(key >> 2)) : lin % nz;
   int e = 0;
   for (int dx = -1; dx <= 1; ++dx)
     for (int dy = -1; dy <= 1; ++dy)
       for (int dz = -1; dz <= 1; ++dz, ++e) {
         const int64_t a = x + dx, b = y + dy, d = z + dz;
         int64_t f = -1;
-        if (a >= 0 && a < nx && b >= 0 && b < ny && d >= 0 && d < nz) f = find_cell(ukeys, m, morton3(a, b, d));
+        if (a >= 0 && a < nx && b >= 0 && b < ny && d >= 0 && d < nz)
+          f = find_cell(ukeys, m, kMorton ? morton3(a, b, d) : static_cast<uint64_t>((a * ny + b) * nz + d));
         nbr[27 * c + e] = static_cast<int32_t>(f);
       }
 }
@@ -1086,29 +1088,76 @@ __device__ V3 fast_eigen3x3(const S3& C) {
 
 constexpr int kNrmK = 32;  // largest max_nn
 
-// The 27 neighbour cells (-1: empty or outside) of every occupied cell of a
-// linear-key grid (key = (ix * ny + iy) * nz + iz), (dx, dy, dz) nesting order.
-__global__ __launch_bounds__(kT) void k_cell_neighbours_lin(const uint64_t* ukeys, int64_t m, int64_t nx, int64_t ny,
-                                                            int64_t nz, int32_t* nbr) {
+// ---------------------------------------------------------- search grid ----
+// The one neighbour-search structure of normals, radius search / FPFH, ICP and
+// RANSAC validation: a cloud sorted into the cells of a linear-key grid (key =
+// (ix * ny + iy) * nz + iz) whose edge is at least the search radius, so the
+// 27 cells around a query's cell hold its ball.  This is the view kernels take
+// by value; SearchGridBufs (host, below) owns the buffers and
+// build_search_grid fills both.
+struct SearchGrid {
+  const double* sxyz;      // the points' coordinates in cell-sorted order
+  const uint32_t* sidx;    // the sorted points' indices in the cloud
+  const uint64_t* skeys;   // the sorted points' cell keys
+  int64_t n;               // points
+  const uint64_t* ukeys;   // the occupied cells' keys, ascending
+  const uint32_t* ustart;  // the occupied cells' first sorted position
+  int64_t m;               // occupied cells
+  const int32_t* nbr;      // self-queries: 27 neighbour cells per occupied cell (or null)
+  const int32_t* dense;    // foreign queries: key -> occupied cell, -1: empty (null: binary search)
+  Grid g;                  // (last: the self-query kernels read one 64-byte run of kernel arguments)
+};
+
+// dense cell table (ICP's and RANSAC validation's): dense[key] = occupied-cell index (pre-filled with -1)
+__global__ __launch_bounds__(kT) void k_icp_dense(const uint64_t* ukeys, int64_t m, int32_t* dense) {
   const int64_t c = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
-  if (c >= m) return;
-  const int64_t key = static_cast<int64_t>(ukeys[c]);
-  const int64_t x = key / (ny * nz), y = (key / nz) % ny, z = key % nz;
-  int e = 0;
-  for (int dx = -1; dx <= 1; ++dx)
-    for (int dy = -1; dy <= 1; ++dy)
-      for (int dz = -1; dz <= 1; ++dz, ++e) {
-        const int64_t a = x + dx, b = y + dy, d = z + dz;
-        int64_t f = -1;
-        if (a >= 0 && a < nx && b >= 0 && b < ny && d >= 0 && d < nz)
-          f = find_cell(ukeys, m, static_cast<uint64_t>((a * ny + b) * nz + d));
-        nbr[27 * c + e] = static_cast<int32_t>(f);
-      }
+  if (c < m) dense[ukeys[c]] = static_cast<int32_t>(c);
+}
+
+// The nearest grid point of a foreign point q within the search radius:
+// ((dx^2 + dy^2) + dz^2) < r2 (nanoflann's strict radius test), the least
+// (d2, point index); candidates from the 27 cells around q's cell.  -> its
+// index (-1: none), *d2out (0 when none).
+__device__ __forceinline__ int64_t grid_nn(double q0, double q1, double q2, const SearchGrid& sg, double r2,
+                                           double* d2out) {
+  const Grid& g = sg.g;
+  double bd = INFINITY;
+  int64_t bi = -1;
+  const double f0 = floor((q0 - g.lo0) / g.h), f1 = floor((q1 - g.lo1) / g.h), f2 = floor((q2 - g.lo2) / g.h);
+  // a query more than a cell outside the grid (or not finite) has no candidate cell
+  if (f0 >= -1.0 && f0 <= static_cast<double>(g.nx) && f1 >= -1.0 && f1 <= static_cast<double>(g.ny) &&
+      f2 >= -1.0 && f2 <= static_cast<double>(g.nz)) {
+    const int64_t ix = static_cast<int64_t>(f0), iy = static_cast<int64_t>(f1), iz = static_cast<int64_t>(f2);
+    for (int dx = -1; dx <= 1; ++dx)
+      for (int dy = -1; dy <= 1; ++dy)
+        for (int dz = -1; dz <= 1; ++dz) {
+          const int64_t a = ix + dx, b = iy + dy, d = iz + dz;
+          if (a < 0 || a >= g.nx || b < 0 || b >= g.ny || d < 0 || d >= g.nz) continue;
+          const uint64_t key = static_cast<uint64_t>((a * g.ny + b) * g.nz + d);
+          const int64_t cc = sg.dense ? static_cast<int64_t>(sg.dense[key]) : find_cell(sg.ukeys, sg.m, key);
+          if (cc < 0) continue;
+          const int64_t t1 = cc + 1 < sg.m ? static_cast<int64_t>(sg.ustart[cc + 1]) : sg.n;
+          for (int64_t t = sg.ustart[cc]; t < t1; ++t) {
+            const double d0 = q0 - sg.sxyz[3 * t], d1 = q1 - sg.sxyz[3 * t + 1], d2 = q2 - sg.sxyz[3 * t + 2];
+            const double dd = (d0 * d0 + d1 * d1) + d2 * d2;
+            if (!(dd < r2)) continue;
+            const int64_t id = sg.sidx[t];
+            if (dd < bd || (dd == bd && id < bi)) {
+              bd = dd;
+              bi = id;
+            }
+          }
+        }
+  }
+  *d2out = bi >= 0 ? bd : 0.0;
+  return bi;
 }
 
 // One query per thread, in cell-sorted order (neighbouring threads share
 // cells).  Candidates from the 27 cells of edge >= radius around the query's
-// cell; the max_nn best by (d2, index) in a sorted register list.
+// cell; the max_nn best by (d2, index) in a sorted register list.  It takes
+// the SearchGrid's self-query members as loose arguments: passed as the view,
+// the same loop measured 0.03-0.05 ms (0.3-0.5 %) slower on 3.38 M points.
 __global__ __launch_bounds__(kT) void k_normals(const double* xyz, const double* sxyz, const uint32_t* sidx,
                                                 const uint64_t* skeys, int64_t n, const uint64_t* ukeys,
                                                 const uint32_t* ustart, int64_t m, const int32_t* nbr, double r2,
@@ -1211,53 +1260,13 @@ __global__ __launch_bounds__(kT) void k_fill_up(double* out, int64_t n) {
 constexpr int kIcpBlock = 64;  // source points per fold thread
 constexpr int kIcpSums = 29;   // JTJ upper triangle (21), JTr (6), sum of d^2, correspondences
 
-// dense cell table: dense[key] = occupied-cell index (pre-filled with -1)
-__global__ __launch_bounds__(kT) void k_icp_dense(const uint64_t* ukeys, int64_t m, int32_t* dense) {
-  const int64_t c = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
-  if (c < m) dense[ukeys[c]] = static_cast<int32_t>(c);
-}
-
-// Nearest target point of every source point q within max_distance:
-// ((dx^2 + dy^2) + dz^2) < r2 (nanoflann's strict radius test), the least
-// (d2, target index); candidates from the 27 cells (edge >= max_distance)
-// around q's cell.  -> corr[i] (target index or -1), dist2[i].
-__global__ __launch_bounds__(kT) void k_icp_corr(const double* cur, int64_t n, Grid g, const int32_t* dense,
-                                                 const uint64_t* ukeys, int64_t m, const uint32_t* ustart,
-                                                 int64_t nt, const double* sxyz, const uint32_t* sidx, double r2,
+// Nearest target point (grid_nn: cells of edge >= max_distance) of every
+// source point within max_distance -> corr[i] (target index or -1), dist2[i].
+__global__ __launch_bounds__(kT) void k_icp_corr(const double* cur, int64_t n, SearchGrid tg, double r2,
                                                  int32_t* corr, double* dist2) {
   const int64_t i = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
   if (i >= n) return;
-  const double q0 = cur[3 * i], q1 = cur[3 * i + 1], q2 = cur[3 * i + 2];
-  double bd = INFINITY;
-  int64_t bi = -1;
-  const double f0 = floor((q0 - g.lo0) / g.h), f1 = floor((q1 - g.lo1) / g.h), f2 = floor((q2 - g.lo2) / g.h);
-  // a query more than a cell outside the grid (or not finite) has no candidate cell
-  if (f0 >= -1.0 && f0 <= static_cast<double>(g.nx) && f1 >= -1.0 && f1 <= static_cast<double>(g.ny) &&
-      f2 >= -1.0 && f2 <= static_cast<double>(g.nz)) {
-    const int64_t ix = static_cast<int64_t>(f0), iy = static_cast<int64_t>(f1), iz = static_cast<int64_t>(f2);
-    for (int dx = -1; dx <= 1; ++dx)
-      for (int dy = -1; dy <= 1; ++dy)
-        for (int dz = -1; dz <= 1; ++dz) {
-          const int64_t a = ix + dx, b = iy + dy, d = iz + dz;
-          if (a < 0 || a >= g.nx || b < 0 || b >= g.ny || d < 0 || d >= g.nz) continue;
-          const uint64_t key = static_cast<uint64_t>((a * g.ny + b) * g.nz + d);
-          const int64_t cc = dense ? static_cast<int64_t>(dense[key]) : find_cell(ukeys, m, key);
-          if (cc < 0) continue;
-          const int64_t t1 = cc + 1 < m ? static_cast<int64_t>(ustart[cc + 1]) : nt;
-          for (int64_t t = ustart[cc]; t < t1; ++t) {
-            const double d0 = q0 - sxyz[3 * t], d1 = q1 - sxyz[3 * t + 1], d2 = q2 - sxyz[3 * t + 2];
-            const double dd = (d0 * d0 + d1 * d1) + d2 * d2;
-            if (!(dd < r2)) continue;
-            const int64_t id = sidx[t];
-            if (dd < bd || (dd == bd && id < bi)) {
-              bd = dd;
-              bi = id;
-            }
-          }
-        }
-  }
-  corr[i] = static_cast<int32_t>(bi);
-  dist2[i] = bi >= 0 ? bd : 0.0;
+  corr[i] = static_cast<int32_t>(grid_nn(cur[3 * i], cur[3 * i + 1], cur[3 * i + 2], tg, r2, &dist2[i]));
 }
 
 // One thread per kIcpBlock source points, in index order: the point-to-plane
@@ -1534,6 +1543,73 @@ int cells(sl_ctx* c, const double* xyz, int64_t n, const Grid& g, DBuf<uint64_t>
   return SL_OK;
 }
 
+// The indices of the set flags, ascending: flag[0..n) -> out_index[0..*count)
+// (pos: n entries of scratch; *count is written once the scan has finished, the
+// compaction is left queued on s).  sl_statistical_outliers has its own copy
+// of these steps.
+int compact_indices(sl_ctx* c, const uint32_t* flag, int64_t n, uint32_t* pos, int64_t* out_index, int64_t* count,
+                    hipStream_t s) {
+  const int r = scan_flags(c, flag, n, pos, count, s);
+  if (r) return r;
+  hipLaunchKernelGGL(k_compact_index, dim3(blocks(n)), dim3(kT), 0, s, flag, pos, n, out_index);
+  MTRY(c, hipGetLastError());
+  return SL_OK;
+}
+
+// Host owner of a SearchGrid: the buffers, and the view kernels take.
+struct SearchGridBufs {
+  DBuf<uint64_t> keys, ukeys;
+  DBuf<uint32_t> idx, ustart;
+  DBuf<double> sxyz;
+  DBuf<int32_t> table;
+  SearchGrid view;
+};
+
+enum class GridTable { kNeighbours, kDense };  // self-queries / foreign queries
+
+constexpr double kGridMaxAxisCells = 1.0e6;            // a cell edge is at least (largest extent) / this
+constexpr int64_t kDenseMaxCells = int64_t{1} << 26;  // a dense cell table up to 256 MB, else binary search
+
+// The search grid of n points with cells of edge >= min_edge, and the table
+// the caller's queries need.  Non-finite coordinates are rejected with the
+// caller's message.  Synchronises s only inside bounds() and cells(); the
+// table kernels are left queued.
+int build_search_grid(sl_ctx* c, const double* xyz, int64_t n, double min_edge, GridTable table,
+                      const char* nonfinite_msg, SearchGridBufs* sb, hipStream_t s) {
+  double b[6];
+  int r = bounds(c, xyz, n, b, s);
+  if (r) return r;
+  double emax = 0.0;
+  for (int k = 0; k < 3; ++k) emax = std::max(emax, b[3 + k] - b[k]);
+  if (!std::isfinite(emax)) return slgpu_fail(c, SL_EINVAL, nonfinite_msg);
+  // (cannot fire: an edge >= extent / 1e6 keeps every axis within 1e6 + 1
+  // cells, below make_grid's 2e6 per axis and 9e18 in all)
+  Grid g;
+  if (!make_grid(b, b + 3, std::max(min_edge, emax / kGridMaxAxisCells), &g))
+    return slgpu_fail(c, SL_EINVAL, "search grid is too large");
+  int64_t m = 0;
+  r = cells(c, xyz, n, g, sb->keys, sb->idx, sb->ukeys, sb->ustart, &m, s);
+  if (r) return r;
+  MTRY(c, sb->sxyz.alloc(3 * n));
+  hipLaunchKernelGGL(k_gather_sorted, dim3(blocks(n)), dim3(kT), 0, s, xyz, sb->idx.p, n, sb->sxyz.p);
+  MTRY(c, hipGetLastError());
+  sb->view = {sb->sxyz.p, sb->idx.p, sb->keys.p, n, sb->ukeys.p, sb->ustart.p, m, nullptr, nullptr, g};
+  const int64_t ncell = (g.nx * g.ny) * g.nz;
+  if (table == GridTable::kNeighbours) {
+    MTRY(c, sb->table.alloc(27 * m));
+    hipLaunchKernelGGL(k_cell_neighbours<false>, dim3(blocks(m)), dim3(kT), 0, s, sb->ukeys.p, m, g.nx, g.ny, g.nz,
+                       sb->table.p);
+    sb->view.nbr = sb->table.p;
+  } else if (ncell <= kDenseMaxCells) {
+    MTRY(c, sb->table.alloc(ncell));
+    MTRY(c, hipMemsetAsync(sb->table.p, 0xff, sizeof(int32_t) * ncell, s));
+    hipLaunchKernelGGL(k_icp_dense, dim3(blocks(m)), dim3(kT), 0, s, sb->ukeys.p, m, sb->table.p);
+    sb->view.dense = sb->table.p;
+  }
+  MTRY(c, hipGetLastError());
+  return SL_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1660,7 +1736,7 @@ int sl_statistical_outliers(sl_ctx* c, const double* xyz, int64_t n, int nb_neig
       MTRY(c, cell0.alloc(n));
       hipLaunchKernelGGL(k_cell_of, dim3(blocks(n)), dim3(kT), 0, s, flag.p, seg.p, n, cell0.p);
       MTRY(c, nbr0.alloc(27 * ml));
-      hipLaunchKernelGGL(k_cell_neighbours, dim3(blocks(ml)), dim3(kT), 0, s, lk[l].p, ml, py.dim[l][0],
+      hipLaunchKernelGGL(k_cell_neighbours<true>, dim3(blocks(ml)), dim3(kT), 0, s, lk[l].p, ml, py.dim[l][0],
                          py.dim[l][1], py.dim[l][2], nbr0.p);
       MTRY(c, hipGetLastError());
     }
@@ -1856,30 +1932,12 @@ int sl_estimate_normals(sl_ctx* c, const double* xyz, int64_t n, double radius, 
     MTRY(c, hipGetLastError());
     return SL_OK;
   }
-  double b[6];
-  int r = bounds(c, xyz, n, b, s);
+  SearchGridBufs sg;
+  const int r = build_search_grid(c, xyz, n, radius, GridTable::kNeighbours, "non-finite point coordinates", &sg, s);
   if (r) return r;
-  double emax = 0.0;
-  for (int k = 0; k < 3; ++k) emax = std::max(emax, b[3 + k] - b[k]);
-  if (!std::isfinite(emax)) return slgpu_fail(c, SL_EINVAL, "non-finite point coordinates");
-  // cells of edge >= radius, so the 27 around a query's cell hold its ball;
-  // at most ~1e6 per axis
-  const double h = std::max(radius, emax / 1.0e6);
-  Grid g;
-  if (!make_grid(b, b + 3, h, &g)) return slgpu_fail(c, SL_EINVAL, "normal-search grid is too large");
-  DBuf<uint64_t> keys, ukeys;
-  DBuf<uint32_t> idx, ustart;
-  int64_t m = 0;
-  r = cells(c, xyz, n, g, keys, idx, ukeys, ustart, &m, s);
-  if (r) return r;
-  DBuf<double> sxyz;
-  DBuf<int32_t> nbr;
-  MTRY(c, sxyz.alloc(3 * n));
-  MTRY(c, nbr.alloc(27 * m));
-  hipLaunchKernelGGL(k_gather_sorted, dim3(blocks(n)), dim3(kT), 0, s, xyz, idx.p, n, sxyz.p);
-  hipLaunchKernelGGL(k_cell_neighbours_lin, dim3(blocks(m)), dim3(kT), 0, s, ukeys.p, m, g.nx, g.ny, g.nz, nbr.p);
-  hipLaunchKernelGGL(k_normals, dim3(blocks(n)), dim3(kT), 0, s, xyz, sxyz.p, idx.p, keys.p, n, ukeys.p, ustart.p, m,
-                     nbr.p, r2, max_nn, normals);
+  const SearchGrid& v = sg.view;
+  hipLaunchKernelGGL(k_normals, dim3(blocks(n)), dim3(kT), 0, s, xyz, v.sxyz, v.sidx, v.skeys, v.n, v.ukeys, v.ustart,
+                     v.m, v.nbr, r2, max_nn, normals);
   MTRY(c, hipGetLastError());
   MTRY(c, hipStreamSynchronize(s));
   return SL_OK;
@@ -2018,32 +2076,11 @@ int sl_icp_point_to_plane(sl_ctx* c, const double* source, int64_t n_src, const 
   MTRY(c, hipSetDevice(slgpu_device(c)));
   // the target's cell grid (cells of edge >= max_distance: the 27 around a
   // query's cell hold its ball)
-  double bnd[6];
-  int r = bounds(c, target, n_tgt, bnd, s);
+  SearchGridBufs tg;
+  int r = build_search_grid(c, target, n_tgt, max_distance, GridTable::kDense, "non-finite target coordinates", &tg, s);
   if (r) return r;
-  double emax = 0.0;
-  for (int k = 0; k < 3; ++k) emax = std::max(emax, bnd[3 + k] - bnd[k]);
-  if (!std::isfinite(emax)) return slgpu_fail(c, SL_EINVAL, "non-finite target coordinates");
-  Grid g;
-  if (!make_grid(bnd, bnd + 3, std::max(max_distance, emax / 1.0e6), &g))
-    return slgpu_fail(c, SL_EINVAL, "correspondence grid is too large");
-  DBuf<uint64_t> keys, ukeys;
-  DBuf<uint32_t> idx, ustart;
-  int64_t m = 0;
-  r = cells(c, target, n_tgt, g, keys, idx, ukeys, ustart, &m, s);
-  if (r) return r;
-  DBuf<double> sxyz, cur, d2, part, dmat;
-  DBuf<int32_t> corr, dense;
-  MTRY(c, sxyz.alloc(3 * n_tgt));
-  hipLaunchKernelGGL(k_gather_sorted, dim3(blocks(n_tgt)), dim3(kT), 0, s, target, idx.p, n_tgt, sxyz.p);
-  MTRY(c, hipGetLastError());
-  const int64_t ncell = (g.nx * g.ny) * g.nz;
-  if (ncell <= (int64_t{1} << 26)) {  // a dense cell table (<= 256 MB), else binary search
-    MTRY(c, dense.alloc(ncell));
-    MTRY(c, hipMemsetAsync(dense.p, 0xff, sizeof(int32_t) * ncell, s));
-    hipLaunchKernelGGL(k_icp_dense, dim3(blocks(m)), dim3(kT), 0, s, ukeys.p, m, dense.p);
-    MTRY(c, hipGetLastError());
-  }
+  DBuf<double> cur, d2, part, dmat;
+  DBuf<int32_t> corr;
   const int64_t nb = (n_src + kIcpBlock - 1) / kIcpBlock;
   MTRY(c, cur.alloc(3 * n_src));
   MTRY(c, d2.alloc(n_src));
@@ -2066,8 +2103,7 @@ int sl_icp_point_to_plane(sl_ctx* c, const double* source, int64_t n_src, const 
   if (!ident && (r = move(T))) return r;
   const double r2 = max_distance * max_distance;
   auto evaluate = [&]() -> int {
-    hipLaunchKernelGGL(k_icp_corr, dim3(blocks(n_src)), dim3(kT), 0, s, cur.p, n_src, g, dense.p, ukeys.p, m,
-                       ustart.p, n_tgt, sxyz.p, idx.p, r2, corr.p, d2.p);
+    hipLaunchKernelGGL(k_icp_corr, dim3(blocks(n_src)), dim3(kT), 0, s, cur.p, n_src, tg.view, r2, corr.p, d2.p);
     hipLaunchKernelGGL(k_icp_fold, dim3(blocks(nb)), dim3(kT), 0, s, cur.p, n_src, target, target_normals, corr.p,
                        d2.p, part.p);
     MTRY(c, hipGetLastError());

@@ -461,11 +461,9 @@ int sl_segment_plane(sl_ctx* c, const double* xyz, int64_t n, double distance_th
                      nt ? distance_threshold : -1.0, flag.p, nflag.p);
   MTRY(c, hipGetLastError());
   int64_t m = 0;
-  int r = scan_flags(c, flag.p, n, pos.p, &m, s);
+  int r = compact_indices(c, flag.p, n, pos.p, inlier_index, &m, s);
   if (r) return r;
   if (nt && m != best_cnt) return slgpu_fail(c, SL_EHIP, "sl_segment_plane: inlier count changed between passes");
-  hipLaunchKernelGGL(k_compact_index, dim3(blocks(n)), dim3(kT), 0, s, flag.p, pos.p, n, inlier_index);
-  MTRY(c, hipGetLastError());
   *n_inliers = m;
 
   // plane_model: the fit over the inliers
@@ -491,10 +489,7 @@ int sl_segment_plane(sl_ctx* c, const double* xyz, int64_t n, double distance_th
   }
   if (rest_index) {
     int64_t rest = 0;
-    r = scan_flags(c, nflag.p, n, pos.p, &rest, s);
-    if (r) return r;
-    hipLaunchKernelGGL(k_compact_index, dim3(blocks(n)), dim3(kT), 0, s, nflag.p, pos.p, n, rest_index);
-    MTRY(c, hipGetLastError());
+    if ((r = compact_indices(c, nflag.p, n, pos.p, rest_index, &rest, s))) return r;
   }
   MTRY(c, hipStreamSynchronize(s));
   return SL_OK;
@@ -517,10 +512,8 @@ int sl_index_complement(sl_ctx* c, const int64_t* index, int64_t m, int64_t n, i
   hipLaunchKernelGGL(k_fill_ones, dim3(blocks(n)), dim3(kT), 0, s, flag.p, n);
   if (m) hipLaunchKernelGGL(k_unmark, dim3(blocks(m)), dim3(kT), 0, s, index, m, n, flag.p);
   MTRY(c, hipGetLastError());
-  const int r = scan_flags(c, flag.p, n, pos.p, out_n, s);
+  const int r = compact_indices(c, flag.p, n, pos.p, out_index, out_n, s);
   if (r) return r;
-  hipLaunchKernelGGL(k_compact_index, dim3(blocks(n)), dim3(kT), 0, s, flag.p, pos.p, n, out_index);
-  MTRY(c, hipGetLastError());
   MTRY(c, hipStreamSynchronize(s));
   return SL_OK;
 }

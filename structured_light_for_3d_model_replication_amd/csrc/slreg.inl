@@ -338,21 +338,10 @@ __device__ void nn_sort(double* s_d, uint32_t* s_i, int P, int lane) {
     }
 }
 
-struct CellSet {  // the sorted points' cell structure (slmerge.hip's cells())
-  const double* sxyz;
-  const uint32_t* sidx;
-  const uint64_t* skeys;
-  int64_t n;
-  const uint64_t* ukeys;
-  const uint32_t* ustart;
-  int64_t m;
-  const int32_t* nbr;  // 27 neighbour cells per occupied cell
-};
-
 // fn(t, dd, pass) for every candidate of the 27 cells around sorted point j,
 // 64 at a time (wave-uniform calls; pass: d2 < r2 and t in range)
 template <class F>
-__device__ __forceinline__ void nn_scan(const CellSet& cs, int64_t j, double r2, int lane, F&& fn) {
+__device__ __forceinline__ void nn_scan(const SearchGrid& cs, int64_t j, double r2, int lane, F&& fn) {
   const double q0 = cs.sxyz[3 * j], q1 = cs.sxyz[3 * j + 1], q2 = cs.sxyz[3 * j + 2];
   const int64_t cell = find_cell(cs.ukeys, cs.m, cs.skeys[j]);
   for (int e = 0; e < 27; ++e) {
@@ -373,7 +362,7 @@ __device__ __forceinline__ void nn_scan(const CellSet& cs, int64_t j, double r2,
   }
 }
 
-__device__ __forceinline__ void nn_write(const CellSet& cs, int64_t j, const double* s_d, const uint32_t* s_i,
+__device__ __forceinline__ void nn_write(const SearchGrid& cs, int64_t j, const double* s_d, const uint32_t* s_i,
                                          int found, int max_nn, int lane, int32_t* out_idx, double* out_d2,
                                          int32_t* out_cnt) {
   const int64_t i = cs.sidx[j];
@@ -389,8 +378,8 @@ __device__ __forceinline__ void nn_write(const CellSet& cs, int64_t j, const dou
 // query (sorted order); in-radius candidates compacted into LDS by ballots,
 // sorted, the first max_nn written -> out_idx / out_d2 [n][max_nn], out_cnt[n].
 // More than kNnCap candidates: the query goes to ovf (k_radius_nn_select).
-__global__ __launch_bounds__(64) void k_radius_nn(CellSet cs, double r2, int max_nn, int32_t* out_idx, double* out_d2,
-                                                  int32_t* out_cnt, uint32_t* ovf, unsigned* n_ovf) {
+__global__ __launch_bounds__(64) void k_radius_nn(SearchGrid cs, double r2, int max_nn, int32_t* out_idx,
+                                                  double* out_d2, int32_t* out_cnt, uint32_t* ovf, unsigned* n_ovf) {
   __shared__ double s_d[kNnCap];
   __shared__ uint32_t s_i[kNnCap];
   const int64_t j = blockIdx.x;
@@ -427,7 +416,7 @@ __global__ __launch_bounds__(64) void k_radius_nn(CellSet cs, double r2, int max
 // max_nn-th smallest d2 K by a radix select over its bit pattern (d2 >= 0:
 // ordered as an integer), then among the ties d2 == K the smallest indices;
 // those max_nn entries sorted and written as k_radius_nn does.
-__global__ __launch_bounds__(64) void k_radius_nn_select(CellSet cs, double r2, int max_nn, const uint32_t* ovf,
+__global__ __launch_bounds__(64) void k_radius_nn_select(SearchGrid cs, double r2, int max_nn, const uint32_t* ovf,
                                                          int32_t* out_idx, double* out_d2, int32_t* out_cnt) {
   __shared__ double s_d[kNnMax];
   __shared__ uint32_t s_i[kNnMax];
@@ -695,56 +684,10 @@ __global__ __launch_bounds__(kT) void k_reg_hyp(RegIn in, int64_t it0, int64_t c
   for (int k = 0; k < 12; ++k) Tout[12 * h + k] = T[k];
 }
 
-// The nearest target point (cell grid, d2 < r2; least (d2, index)) of the
-// point q -> its index (-1: none), *d2.
-__device__ __forceinline__ int64_t grid_nn(double q0, double q1, double q2, const Grid& g, const int32_t* dense,
-                                           const uint64_t* ukeys, int64_t m, const uint32_t* ustart, int64_t nt,
-                                           const double* sxyz, const uint32_t* sidx, double r2, double* d2out) {
-  double bd = INFINITY;
-  int64_t bi = -1;
-  const double f0 = floor((q0 - g.lo0) / g.h), f1 = floor((q1 - g.lo1) / g.h), f2 = floor((q2 - g.lo2) / g.h);
-  if (f0 >= -1.0 && f0 <= static_cast<double>(g.nx) && f1 >= -1.0 && f1 <= static_cast<double>(g.ny) &&
-      f2 >= -1.0 && f2 <= static_cast<double>(g.nz)) {
-    const int64_t ix = static_cast<int64_t>(f0), iy = static_cast<int64_t>(f1), iz = static_cast<int64_t>(f2);
-    for (int dx = -1; dx <= 1; ++dx)
-      for (int dy = -1; dy <= 1; ++dy)
-        for (int dz = -1; dz <= 1; ++dz) {
-          const int64_t a = ix + dx, b = iy + dy, d = iz + dz;
-          if (a < 0 || a >= g.nx || b < 0 || b >= g.ny || d < 0 || d >= g.nz) continue;
-          const uint64_t key = static_cast<uint64_t>((a * g.ny + b) * g.nz + d);
-          const int64_t cc = dense ? static_cast<int64_t>(dense[key]) : find_cell(ukeys, m, key);
-          if (cc < 0) continue;
-          const int64_t t1 = cc + 1 < m ? static_cast<int64_t>(ustart[cc + 1]) : nt;
-          for (int64_t t = ustart[cc]; t < t1; ++t) {
-            const double d0 = q0 - sxyz[3 * t], d1 = q1 - sxyz[3 * t + 1], d2 = q2 - sxyz[3 * t + 2];
-            const double dd = (d0 * d0 + d1 * d1) + d2 * d2;
-            if (!(dd < r2)) continue;
-            const int64_t id = sidx[t];
-            if (dd < bd || (dd == bd && id < bi)) {
-              bd = dd;
-              bi = id;
-            }
-          }
-        }
-  }
-  *d2out = bi >= 0 ? bd : 0.0;
-  return bi;
-}
-
-struct TgtGrid {
-  Grid g;
-  const int32_t* dense;
-  const uint64_t* ukeys;
-  int64_t m;
-  const uint32_t* ustart;
-  const double* sxyz;
-  const uint32_t* sidx;
-};
-
 // GetRegistrationResultAndCorrespondences for hypotheses hyp[0..P): grid
 // (source points / 256, P); every moved source point's nearest target within
-// max_dist -> e2 / ok [P][ns]
-__global__ __launch_bounds__(kT) void k_reg_validate(RegIn in, TgtGrid tg, const int32_t* hyp, const double* Tall,
+// max_dist (grid_nn) -> e2 / ok [P][ns]
+__global__ __launch_bounds__(kT) void k_reg_validate(RegIn in, SearchGrid tg, const int32_t* hyp, const double* Tall,
                                                      double* e2, uint8_t* ok) {
   const int64_t i = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
   const int p = blockIdx.y;
@@ -752,8 +695,7 @@ __global__ __launch_bounds__(kT) void k_reg_validate(RegIn in, TgtGrid tg, const
   const double* T = Tall + 12 * static_cast<int64_t>(hyp[p]);
   const reg::D3 q = reg::tp(T, reg::ld3(in.src, i));
   double d2;
-  const int64_t bi = grid_nn(q.x, q.y, q.z, tg.g, tg.dense, tg.ukeys, tg.m, tg.ustart, in.nt, tg.sxyz, tg.sidx,
-                             in.max_dist * in.max_dist, &d2);
+  const int64_t bi = grid_nn(q.x, q.y, q.z, tg, in.max_dist * in.max_dist, &d2);
   e2[p * in.ns + i] = d2;
   ok[p * in.ns + i] = bi >= 0 ? 1 : 0;
 }
@@ -822,30 +764,14 @@ int radius_lists(sl_ctx* c, const double* xyz, int64_t n, double radius, int max
     MTRY(c, hipStreamSynchronize(s));
     return SL_OK;
   }
-  double b[6];
-  int r = bounds(c, xyz, n, b, s);
-  if (r) return r;
-  double emax = 0.0;
-  for (int k = 0; k < 3; ++k) emax = std::max(emax, b[3 + k] - b[k]);
-  if (!std::isfinite(emax)) return slgpu_fail(c, SL_EINVAL, "non-finite point coordinates");
-  Grid g;
-  if (!make_grid(b, b + 3, std::max(radius, emax / 1.0e6), &g))
-    return slgpu_fail(c, SL_EINVAL, "radius-search grid is too large");
-  DBuf<uint64_t> keys, ukeys;
-  DBuf<uint32_t> sidx, ustart, ovf, novf;
-  int64_t m = 0;
-  r = cells(c, xyz, n, g, keys, sidx, ukeys, ustart, &m, s);
-  if (r) return r;
-  DBuf<double> sxyz;
-  DBuf<int32_t> nbr;
-  MTRY(c, sxyz.alloc(3 * n));
-  MTRY(c, nbr.alloc(27 * m));
+  DBuf<uint32_t> ovf, novf;
   MTRY(c, ovf.alloc(n));
   MTRY(c, novf.alloc(1));
   MTRY(c, hipMemsetAsync(novf.p, 0, sizeof(uint32_t), s));
-  hipLaunchKernelGGL(k_gather_sorted, dim3(blocks(n)), dim3(kT), 0, s, xyz, sidx.p, n, sxyz.p);
-  hipLaunchKernelGGL(k_cell_neighbours_lin, dim3(blocks(m)), dim3(kT), 0, s, ukeys.p, m, g.nx, g.ny, g.nz, nbr.p);
-  const CellSet cs{sxyz.p, sidx.p, keys.p, n, ukeys.p, ustart.p, m, nbr.p};
+  SearchGridBufs sg;
+  const int r = build_search_grid(c, xyz, n, radius, GridTable::kNeighbours, "non-finite point coordinates", &sg, s);
+  if (r) return r;
+  const SearchGrid& cs = sg.view;
   hipLaunchKernelGGL(k_radius_nn, dim3(static_cast<unsigned>(n)), dim3(64), 0, s, cs, r2, max_nn, idx_out, d2_out,
                      cnt_out, ovf.p, novf.p);
   MTRY(c, hipGetLastError());
@@ -990,33 +916,11 @@ int sl_ransac_feature_matching(sl_ctx* c, const double* source, int64_t ns, cons
   MTRY(c, dcor.alloc(2 * nc));
   MTRY(c, hipMemcpyAsync(dcor.p, cor.data(), sizeof(int32_t) * 2 * nc, hipMemcpyHostToDevice, s));
   // the target's cell grid (cells of edge >= max_distance)
-  double bnd[6];
-  int r = bounds(c, target, nt, bnd, s);
+  SearchGridBufs tgb;
+  const int r = build_search_grid(c, target, nt, max_distance, GridTable::kDense, "non-finite target coordinates",
+                                  &tgb, s);
   if (r) return r;
-  double emax = 0.0;
-  for (int k = 0; k < 3; ++k) emax = std::max(emax, bnd[3 + k] - bnd[k]);
-  if (!std::isfinite(emax)) return slgpu_fail(c, SL_EINVAL, "non-finite target coordinates");
-  Grid g;
-  if (!make_grid(bnd, bnd + 3, std::max(max_distance, emax / 1.0e6), &g))
-    return slgpu_fail(c, SL_EINVAL, "correspondence grid is too large");
-  DBuf<uint64_t> keys, ukeys;
-  DBuf<uint32_t> idx, ustart;
-  int64_t m = 0;
-  r = cells(c, target, nt, g, keys, idx, ukeys, ustart, &m, s);
-  if (r) return r;
-  DBuf<double> sxyz;
-  DBuf<int32_t> dense;
-  MTRY(c, sxyz.alloc(3 * nt));
-  hipLaunchKernelGGL(k_gather_sorted, dim3(blocks(nt)), dim3(kT), 0, s, target, idx.p, nt, sxyz.p);
-  MTRY(c, hipGetLastError());
-  const int64_t ncell = (g.nx * g.ny) * g.nz;
-  if (ncell <= (int64_t{1} << 26)) {
-    MTRY(c, dense.alloc(ncell));
-    MTRY(c, hipMemsetAsync(dense.p, 0xff, sizeof(int32_t) * ncell, s));
-    hipLaunchKernelGGL(k_icp_dense, dim3(blocks(m)), dim3(kT), 0, s, ukeys.p, m, dense.p);
-    MTRY(c, hipGetLastError());
-  }
-  const TgtGrid tg{g, dense.p, ukeys.p, m, ustart.p, sxyz.p, idx.p};
+  const SearchGrid& tg = tgb.view;
   const RegIn in{source, target, ns, nt, dcor.p, nc, seed, edge_similarity, max_distance};
   // hypotheses in batches; validations in chunks of at most kVal (and
   // kVal * ns <= 2^25 scratch entries), walked in iteration order

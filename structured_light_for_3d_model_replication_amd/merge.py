@@ -57,6 +57,12 @@ def _engine(device) -> core.Reconstructor:
         return _engines[idx]
 
 
+def _call(eng, name, *args):
+    """One libslgpu entry point of the (ctx, ..., stream) shape, under the engine's lock, checked."""
+    with eng._lock:
+        _lib.check(getattr(eng._L, name)(eng._ctx, *args, eng._stream(None)), eng._ctx, name)
+
+
 def _f64(points, dev) -> torch.Tensor:
     P = torch.as_tensor(points)
     if P.dim() != 2 or P.shape[1] != 3:
@@ -86,10 +92,7 @@ def voxel_down_sample(points, colors=None, voxel_size: float = 0.02, *, device=N
     out = torch.empty((max(n, 1), 3), dtype=torch.float64, device=eng.device)
     oc = None if C is None else torch.empty((max(n, 1), 3), dtype=torch.uint8, device=eng.device)
     m = ctypes.c_int64()
-    with eng._lock:
-        _lib.check(eng._L.sl_voxel_downsample(eng._ctx, _ptr(P), _ptr(C), n, float(voxel_size), out.data_ptr(),
-                                              _ptr(oc), ctypes.byref(m), eng._stream(None)),
-                   eng._ctx, "sl_voxel_downsample")
+    _call(eng, "sl_voxel_downsample", _ptr(P), _ptr(C), n, float(voxel_size), out.data_ptr(), _ptr(oc), ctypes.byref(m))
     k = m.value
     return out[:k], (None if oc is None else oc[:k])
 
@@ -102,11 +105,8 @@ def remove_statistical_outlier(points, nb_neighbors: int = 20, std_ratio: float 
     avg = torch.empty(max(n, 1), dtype=torch.float64, device=eng.device)
     ind = torch.empty(max(n, 1), dtype=torch.int64, device=eng.device)
     k = ctypes.c_int64()
-    with eng._lock:
-        _lib.check(eng._L.sl_statistical_outliers(eng._ctx, _ptr(P), n, int(nb_neighbors), float(std_ratio),
-                                                  avg.data_ptr(), ind.data_ptr(), ctypes.byref(k),
-                                                  eng._stream(None)),
-                   eng._ctx, "sl_statistical_outliers")
+    _call(eng, "sl_statistical_outliers", _ptr(P), n, int(nb_neighbors), float(std_ratio), avg.data_ptr(),
+          ind.data_ptr(), ctypes.byref(k))
     return ind[: k.value], avg[:n]
 
 
@@ -124,17 +124,13 @@ def select_by_index(points, colors, ind, invert: bool = False, *, device=None):
         n = P.shape[0]
         rest = torch.empty(max(n, 1), dtype=torch.int64, device=eng.device)
         k = ctypes.c_int64()
-        with eng._lock:
-            _lib.check(eng._L.sl_index_complement(eng._ctx, I.data_ptr() if I.shape[0] else None, I.shape[0], n,
-                                                  rest.data_ptr(), ctypes.byref(k), eng._stream(None)),
-                       eng._ctx, "sl_index_complement")
+        _call(eng, "sl_index_complement", I.data_ptr() if I.shape[0] else None, I.shape[0], n, rest.data_ptr(),
+              ctypes.byref(k))
         I = rest[: k.value]
     m = I.shape[0]
     out = torch.empty((max(m, 1), 3), dtype=torch.float64, device=eng.device)
     oc = None if C is None else torch.empty((max(m, 1), 3), dtype=torch.uint8, device=eng.device)
-    with eng._lock:
-        _lib.check(eng._L.sl_select_by_index(eng._ctx, _ptr(P), _ptr(C), I.data_ptr(), m, out.data_ptr(), _ptr(oc),
-                                             eng._stream(None)), eng._ctx, "sl_select_by_index")
+    _call(eng, "sl_select_by_index", _ptr(P), _ptr(C), I.data_ptr(), m, out.data_ptr(), _ptr(oc))
     return out[:m], (None if oc is None else oc[:m])
 
 
@@ -161,12 +157,10 @@ def segment_plane(points, distance_threshold, ransac_n: int = 3, num_iterations:
     rest = torch.empty(max(n, 1), dtype=torch.int64, device=eng.device)
     plane = np.zeros(4)
     k, it = ctypes.c_int64(), ctypes.c_int()
-    with eng._lock:
-        _lib.check(eng._L.sl_segment_plane(
-            eng._ctx, _ptr(P) if n else None, n, float(distance_threshold), int(ransac_n), int(num_iterations),
-            float(probability), int(seed) & ((1 << 64) - 1), int(batch),
-            plane.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), inl.data_ptr(), ctypes.byref(k), rest.data_ptr(),
-            ctypes.byref(it), eng._stream(None)), eng._ctx, "sl_segment_plane")
+    _call(eng, "sl_segment_plane", _ptr(P) if n else None, n, float(distance_threshold), int(ransac_n),
+          int(num_iterations), float(probability), int(seed) & ((1 << 64) - 1), int(batch),
+          plane.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), inl.data_ptr(), ctypes.byref(k), rest.data_ptr(),
+          ctypes.byref(it))
     return plane, inl[: k.value], {"iterations": it.value, "rest": rest[: n - k.value]}
 
 
@@ -175,9 +169,7 @@ def transform(points, pose, *, device=None) -> torch.Tensor:
     eng = _engine(device)
     P = _f64(points, eng.device).clone()
     M = torch.as_tensor(np.asarray(pose, dtype=np.float64).reshape(16)).to(eng.device)
-    with eng._lock:
-        _lib.check(eng._L.sl_transform_points(eng._ctx, P.data_ptr(), P.shape[0], M.data_ptr(), eng._stream(None)),
-                   eng._ctx, "sl_transform_points")
+    _call(eng, "sl_transform_points", P.data_ptr(), P.shape[0], M.data_ptr())
     return P
 
 
@@ -189,9 +181,7 @@ def estimate_normals(points, radius: float, max_nn: int = 30, *, device=None) ->
     P = _f64(points, eng.device)
     n = P.shape[0]
     out = torch.empty((max(n, 1), 3), dtype=torch.float64, device=eng.device)
-    with eng._lock:
-        _lib.check(eng._L.sl_estimate_normals(eng._ctx, _ptr(P), n, float(radius), int(max_nn), out.data_ptr(),
-                                              eng._stream(None)), eng._ctx, "sl_estimate_normals")
+    _call(eng, "sl_estimate_normals", _ptr(P), n, float(radius), int(max_nn), out.data_ptr())
     return out[:n]
 
 
@@ -214,14 +204,10 @@ def registration_icp(source, target, target_normals, max_correspondence_distance
     M0 = np.ascontiguousarray(np.eye(4) if init is None else np.asarray(init, dtype=np.float64).reshape(4, 4))
     out = np.zeros(16)
     fit, rmse, it = ctypes.c_double(), ctypes.c_double(), ctypes.c_int()
-    with eng._lock:
-        _lib.check(eng._L.sl_icp_point_to_plane(eng._ctx, _ptr(S) if len(S) else None, S.shape[0],
-                                                _ptr(T) if len(T) else None, _ptr(N) if len(N) else None,
-                                                T.shape[0], float(max_correspondence_distance), M0.ctypes.data,
-                                                int(max_iteration), float(relative_fitness), float(relative_rmse),
-                                                out.ctypes.data, ctypes.byref(fit), ctypes.byref(rmse),
-                                                ctypes.byref(it), eng._stream(None)),
-                   eng._ctx, "sl_icp_point_to_plane")
+    _call(eng, "sl_icp_point_to_plane", _ptr(S) if len(S) else None, S.shape[0], _ptr(T) if len(T) else None,
+          _ptr(N) if len(N) else None, T.shape[0], float(max_correspondence_distance), M0.ctypes.data,
+          int(max_iteration), float(relative_fitness), float(relative_rmse), out.ctypes.data, ctypes.byref(fit),
+          ctypes.byref(rmse), ctypes.byref(it))
     return {"transformation": out.reshape(4, 4), "fitness": fit.value, "inlier_rmse": rmse.value,
             "iterations": it.value}
 
@@ -236,10 +222,8 @@ def radius_search(points, radius: float, max_nn: int, *, device=None):
     idx = torch.empty((max(n, 1), max_nn), dtype=torch.int32, device=eng.device)
     d2 = torch.empty((max(n, 1), max_nn), dtype=torch.float64, device=eng.device)
     cnt = torch.empty(max(n, 1), dtype=torch.int32, device=eng.device)
-    with eng._lock:
-        _lib.check(eng._L.sl_radius_search(eng._ctx, _ptr(P), n, float(radius), int(max_nn), idx.data_ptr(),
-                                           d2.data_ptr(), cnt.data_ptr(), eng._stream(None)),
-                   eng._ctx, "sl_radius_search")
+    _call(eng, "sl_radius_search", _ptr(P), n, float(radius), int(max_nn), idx.data_ptr(), d2.data_ptr(),
+          cnt.data_ptr())
     return idx[:n], d2[:n], cnt[:n]
 
 
@@ -254,9 +238,7 @@ def compute_fpfh_feature(points, normals, radius: float, max_nn: int = 100, *, d
         raise ValueError("compute_fpfh_feature needs a normal per point")
     n = P.shape[0]
     out = torch.empty((max(n, 1), 33), dtype=torch.float64, device=eng.device)
-    with eng._lock:
-        _lib.check(eng._L.sl_compute_fpfh(eng._ctx, _ptr(P), _ptr(N), n, float(radius), int(max_nn), out.data_ptr(),
-                                          eng._stream(None)), eng._ctx, "sl_compute_fpfh")
+    _call(eng, "sl_compute_fpfh", _ptr(P), _ptr(N), n, float(radius), int(max_nn), out.data_ptr())
     return out[:n]
 
 
@@ -269,9 +251,7 @@ def feature_nn(a, b, *, device=None) -> torch.Tensor:
     if A.dim() != 2 or B.dim() != 2 or A.shape[1] != 33 or B.shape[1] != 33:
         raise ValueError("features must be [N, 33]")
     out = torch.empty(max(A.shape[0], 1), dtype=torch.int32, device=eng.device)
-    with eng._lock:
-        _lib.check(eng._L.sl_feature_nn(eng._ctx, _ptr(A), A.shape[0], _ptr(B), B.shape[0], 33, out.data_ptr(),
-                                        eng._stream(None)), eng._ctx, "sl_feature_nn")
+    _call(eng, "sl_feature_nn", _ptr(A), A.shape[0], _ptr(B), B.shape[0], 33, out.data_ptr())
     return out[:A.shape[0]]
 
 
@@ -298,13 +278,11 @@ def registration_ransac_based_on_feature_matching(source, target, source_feature
     out = np.zeros(16)
     fit, rmse = ctypes.c_double(), ctypes.c_double()
     it, vals, nc = ctypes.c_int(), ctypes.c_int(), ctypes.c_int64()
-    with eng._lock:
-        _lib.check(eng._L.sl_ransac_feature_matching(
-            eng._ctx, _ptr(S) if len(S) else None, S.shape[0], _ptr(T) if len(T) else None, T.shape[0],
-            _ptr(FS) if len(FS) else None, _ptr(FT) if len(FT) else None, int(bool(mutual_filter)),
-            float(max_correspondence_distance), float(edge_similarity), int(max_iteration), float(confidence),
-            int(seed) & ((1 << 64) - 1), out.ctypes.data, ctypes.byref(fit), ctypes.byref(rmse), ctypes.byref(it),
-            ctypes.byref(vals), ctypes.byref(nc), eng._stream(None)), eng._ctx, "sl_ransac_feature_matching")
+    _call(eng, "sl_ransac_feature_matching", _ptr(S) if len(S) else None, S.shape[0], _ptr(T) if len(T) else None,
+          T.shape[0], _ptr(FS) if len(FS) else None, _ptr(FT) if len(FT) else None, int(bool(mutual_filter)),
+          float(max_correspondence_distance), float(edge_similarity), int(max_iteration), float(confidence),
+          int(seed) & ((1 << 64) - 1), out.ctypes.data, ctypes.byref(fit), ctypes.byref(rmse), ctypes.byref(it),
+          ctypes.byref(vals), ctypes.byref(nc))
     return {"transformation": out.reshape(4, 4), "fitness": fit.value, "inlier_rmse": rmse.value,
             "iterations": it.value, "validations": vals.value, "correspondences": nc.value}
 
@@ -417,14 +395,19 @@ def merge_pro_360(input_folder, output_path, voxel_size: float = 0.02, *, seed_p
         parts_p.append(transform(pcds[i][0], accum, device=eng.device))
         parts_c.append(pcds[i][1])
         down.pop(i - 1, None)
-    merged_p = torch.cat(parts_p)
-    merged_c = torch.cat(parts_c)
+    P, C, N = _finish_merge(parts_p, parts_c, voxel_size, output_path, binary, eng.device)
+    return (P, C, N, transforms) if return_transforms else (P, C, N)
+
+
+def _finish_merge(parts_p, parts_c, voxel_size, output_path, binary, device):
+    """processing.py:169-181: the moved clouds concatenated, post-processed, normals estimated (radius 2 voxel,
+    max_nn 30) and written -> (points, colors, normals) on the device."""
     print("[Merge 360] Post-processing (Downsample + Outlier removal)...")
-    P, C = postprocess(merged_p, merged_c, voxel_size, device=eng.device)
-    N = estimate_normals(P, voxel_size * 2, 30, device=eng.device)
+    P, C = postprocess(torch.cat(parts_p), torch.cat(parts_c), voxel_size, device=device)
+    N = estimate_normals(P, voxel_size * 2, 30, device=device)
     ply.save_ply_open3d(P.cpu().numpy(), C.cpu().numpy(), output_path, normals=N.cpu().numpy(), binary=binary)
     print(f"[Merge 360] Saved merged cloud to {output_path}")
-    return (P, C, N, transforms) if return_transforms else (P, C, N)
+    return P, C, N
 
 
 def pool_trim(device=None) -> int:
@@ -484,11 +467,4 @@ def merge_pro_360_posed(input_folder, output_path, poses, voxel_size: float = 0.
         parts_p.append(transform(P, M, device=eng.device))
         parts_c.append(torch.from_numpy(C).to(eng.device))
     print(f"[Merge 360] Loaded {len(files)} clouds. Applying the given poses...")
-    merged_p = torch.cat(parts_p)
-    merged_c = torch.cat(parts_c)
-    print("[Merge 360] Post-processing (Downsample + Outlier removal)...")
-    P, C = postprocess(merged_p, merged_c, voxel_size, device=eng.device)
-    N = estimate_normals(P, voxel_size * 2, 30, device=eng.device)
-    ply.save_ply_open3d(P.cpu().numpy(), C.cpu().numpy(), output_path, normals=N.cpu().numpy(), binary=binary)
-    print(f"[Merge 360] Saved merged cloud to {output_path}")
-    return P, C, N
+    return _finish_merge(parts_p, parts_c, voxel_size, output_path, binary, eng.device)

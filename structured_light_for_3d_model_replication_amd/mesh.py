@@ -32,7 +32,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .merge import _engine, _f64, _ptr
+from .merge import _call, _engine, _f64, _ptr
 
 _D3 = ctypes.c_double * 3
 MAX_DEPTH = 10  # 2^30 nodes: the scans and the kernels' grid sizes are laid out for it
@@ -67,11 +67,6 @@ def _depth_of(grid) -> int:
 def _origin(origin):
     o = np.ascontiguousarray(np.asarray(origin, dtype=np.float64).reshape(3))
     return _D3(*o.tolist())
-
-
-def _call(eng, name, *args):
-    with eng._lock:
-        _lib.check(getattr(eng._L, name)(eng._ctx, *args, eng._stream(None)), eng._ctx, name)
 
 
 class _Stages:

@@ -211,3 +211,40 @@ def test_feature_nn_nan_inf_and_identical_rows(mg, nb):
     want = ro.feature_nn(A, same)
     assert np.array_equal(want[:5], np.zeros(5)) and want[5] == -1
     np.testing.assert_array_equal(mg.feature_nn(A, same).cpu().numpy(), want)
+
+
+# --------------------------------------------------- non-finite coordinates ----
+def _cube():
+    return np.array([[x, y, z] for x in (0.0, 1.0) for y in (0.0, 1.0) for z in (0.0, 1.0)])
+
+
+_NONFINITE = {
+    "estimate_normals": ("non-finite point coordinates", lambda mg, bad, ok, F: mg.estimate_normals(bad, 1.0, 30)),
+    "radius_search": ("non-finite point coordinates", lambda mg, bad, ok, F: mg.radius_search(bad, 1.0, 16)),
+    "compute_fpfh_feature": ("non-finite point coordinates",
+                             lambda mg, bad, ok, F: mg.compute_fpfh_feature(bad, np.tile([0.0, 0.0, 1.0], (8, 1)),
+                                                                            1.0, 16)),
+    "registration_icp": ("non-finite target coordinates",
+                         lambda mg, bad, ok, F: mg.registration_icp(ok, bad, np.tile([0.0, 0.0, 1.0], (8, 1)), 1.0)),
+    "registration_ransac_based_on_feature_matching": (
+        "non-finite target coordinates",
+        lambda mg, bad, ok, F: mg.registration_ransac_based_on_feature_matching(ok, bad, F[0], F[1], False, 1.0)),
+    "remove_statistical_outlier": ("non-finite or degenerate point cloud",
+                                   lambda mg, bad, ok, F: mg.remove_statistical_outlier(bad)),
+}
+
+
+@pytest.mark.parametrize("entry", list(_NONFINITE))
+def test_nonfinite_coordinates_are_rejected(mg, entry):
+    """The 8 corners of a unit cube with one coordinate +inf (in the target for
+    ICP and RANSAC, whose 8 one-way correspondences reach the grid): every
+    entry point that sorts a cloud into cells raises ValueError with its own
+    message once the bounds are known, before any cell is keyed."""
+    ok = _cube()
+    bad = _cube()
+    bad[5, 1] = np.inf
+    F = np.random.default_rng(7).normal(size=(2, 8, 33))
+    msg, call = _NONFINITE[entry]
+    with pytest.raises(ValueError) as e:
+        call(mg, bad, ok, F)
+    assert str(e.value) == msg
