@@ -335,6 +335,50 @@ int sl_icp_point_to_plane(sl_ctx* ctx, const double* source, int64_t n_src, cons
                           int max_iteration, double relative_fitness, double relative_rmse, double* transformation,
                           double* fitness, double* inlier_rmse, int* iterations, void* stream);
 
+/* ---- loop-closing 360 merge (Old/new360Merge.py:77-137) ----
+ * get_information_matrix_from_point_clouds(source, target, max_distance,
+ * transformation): Open3D's GetInformationMatrixFromPointClouds restated
+ * (csrc/slinfo.inl; parity with Open3D unpinned; tests/posegraph_oracle.py is
+ * the CPU restatement, bit for bit).  source [n_src][3] / target [n_tgt][3]:
+ * device f64.  Every source point is moved by transformation (host, row-major
+ * 4x4, sl_transform_points' order; exactly the identity: not moved); its
+ * correspondence is the nearest target point with d^2 < max_distance^2, lowest
+ * index on ties; a correspondence with the target point (x, y, z) adds G^T G,
+ * G's rows (0, z, -y, 1, 0, 0), (-z, 0, x, 0, 1, 0), (y, -x, 0, 0, 0, 1), entry
+ * (a, c) as (r1[a] r1[c] + r2[a] r2[c]) + r3[a] r3[c].  Sums: source points in
+ * blocks of 64 consecutive indices, a left fold inside each block (unmatched
+ * points skipped), the blocks' partial sums folded left to right on the host.
+ * -> information host[36] (row-major, symmetric) and *correspondences (may be
+ * NULL).  An empty source or target, or no correspondence: the zero matrix.
+ * SL_EINVAL: NULL arguments, 2^31 points or more, max_distance <= 0,
+ * non-finite target coordinates.  Blocking on `stream`. */
+int sl_information_matrix(sl_ctx* ctx, const double* source, int64_t n_src, const double* target, int64_t n_tgt,
+                          double max_distance, const double* transformation, double* information,
+                          int64_t* correspondences, void* stream);
+
+/* global_optimization(pose_graph, GlobalOptimizationLevenbergMarquardt(),
+ * criteria, GlobalOptimizationOption(reference_node)) with every edge certain
+ * (csrc/slposegraph.inl states the algorithm; tests/posegraph_oracle.py
+ * restates it; parity with Open3D unpinned).  Host only: no context, no GPU
+ * call.  poses: n_nodes row-major 4x4 (in/out).  Edge k: edge_source[k],
+ * edge_target[k], edge_transformation + 16 k (source frame -> target frame),
+ * edge_information + 36 k; edge_uncertain (may be NULL): a non-zero entry is
+ * SL_EINVAL, since the line process and edge pruning are not implemented.
+ * Stops at the first of max|b| < min_right_term, |delta| <
+ * min_relative_increment (|x| + min_relative_increment), |r - r_new| <
+ * min_relative_residual_increment r, r < min_residual, max_iteration
+ * (Open3D's defaults: 1e-6 each, 100; max_iteration_lm 20 retries per
+ * iteration).  -> *iterations, *initial_residual, *final_residual (sum of e^T
+ * Lambda e; each may be NULL).  SL_EINVAL: n_nodes < 1, reference_node or an
+ * edge id out of range, NULL arguments.  The dense 6N x 6N system: 3 arrays
+ * of 288 N^2 bytes. */
+int sl_pose_graph_optimize(double* poses, int n_nodes, const int32_t* edge_source, const int32_t* edge_target,
+                           const double* edge_transformation, const double* edge_information,
+                           const uint8_t* edge_uncertain, int n_edges, int reference_node, int max_iteration,
+                           int max_iteration_lm, double min_right_term, double min_relative_increment,
+                           double min_relative_residual_increment, double min_residual, int* iterations,
+                           double* initial_residual, double* final_residual);
+
 /* ---- global registration (merge_pro_360's FPFH + RANSAC, processing.py:79-113) ----
  * Open3D's algorithms restated (parity unpinned: no Open3D in this image;
  * oracle/registration_oracle.py is the CPU restatement, bit-identical).

@@ -40,6 +40,7 @@ EXPORTS = ("sl_abi_version", "sl_ctx_create", "sl_ctx_destroy", "sl_ctx_last_err
            "sl_mesh_splat", "sl_mesh_unfix", "sl_mesh_divergence", "sl_mesh_sample", "sl_ordered_sum",
            "sl_orient_normals", "sl_mesh_extract_count", "sl_mesh_extract_emit", "sl_mesh_remove_vertices",
            "sl_orient_normals_mst", "sl_orient_normals_mst_stats",
+           "sl_information_matrix", "sl_pose_graph_optimize",
            "sl_decode_triangulate_batch", "sl_last_error")
 
 _vp = ctypes.c_void_p
@@ -112,6 +113,11 @@ _SIGS = {
     "sl_orient_normals_mst": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, ctypes.POINTER(_i64),
                                      ctypes.POINTER(_i64), _vp]),
     "sl_orient_normals_mst_stats": (_i32, [ctypes.POINTER(_i32), ctypes.POINTER(_i32), _i32]),
+    "sl_information_matrix": (_i32, [_vp, _vp, _i64, _vp, _i64, ctypes.c_double, _vp, _vp, ctypes.POINTER(_i64),
+                                      _vp]),
+    "sl_pose_graph_optimize": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, ctypes.c_double,
+                                       ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.POINTER(_i32),
+                                       ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     "sl_gather_unique_id": (_i32, [_vp]),
     "sl_gather_init": (_i32, [_vp, _i32, _i32, _vp]),
     "sl_gather_counts": (_i32, [_vp, _i64, _vp, _vp]),

@@ -2152,3 +2152,6 @@ int sl_merge_pool_trim(int device, int64_t* released_bytes) {
 #include "slmesh.inl"
 // consistent tangent-plane normal orientation (kNN-graph MST) for the meshing drop-ins
 #include "slorient.inl"
+// loop-closing 360 merge: the edges' information matrices (GPU) and the pose-graph optimiser (host only)
+#include "slinfo.inl"
+#include "slposegraph.inl"

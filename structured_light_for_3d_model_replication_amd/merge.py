@@ -25,6 +25,14 @@ the relative pose between the two views.
 ``merge_pro_360_posed`` skips registration and takes the poses as they are
 (the same ones ``Reconstructor.decode_triangulate`` applies inside k_cloud).
 
+Closing the loop.  ``merge_360_pose_graph`` is the reference's full-turn
+script (Old/new360Merge.py): neighbouring views and the pair (first, last)
+registered on the full clouds (``full_registration``), each edge weighted by
+``get_information_matrix_from_point_clouds`` (sl_information_matrix,
+csrc/slinfo.inl) and the pose graph optimised by ``global_optimization``
+(sl_pose_graph_optimize, host code, csrc/slposegraph.inl).  Parity vs Open3D
+unpinned; tests/posegraph_oracle.py restates both.
+
 Clean-up before the merge.  ``segment_plane`` (sl_segment_plane,
 csrc/slplane.inl) is the plane RANSAC of ``remove_background``
 (processing.py:25-52); ``processing.py`` of this package is the drop-in for the
@@ -468,3 +476,176 @@ def merge_pro_360_posed(input_folder, output_path, poses, voxel_size: float = 0.
         parts_c.append(torch.from_numpy(C).to(eng.device))
     print(f"[Merge 360] Loaded {len(files)} clouds. Applying the given poses...")
     return _finish_merge(parts_p, parts_c, voxel_size, output_path, binary, eng.device)
+
+
+# ------------------------------------------------- loop-closing 360 merge ----
+# Old/new360Merge.py:77-178 (and Old/360Merge.py:19-84): every pair of
+# neighbouring views and the closing pair (first, last) registered, each edge
+# weighted by its information matrix, and the closing error spread over the
+# ring by pose-graph optimisation.  Open3D's algorithms restated
+# (csrc/slinfo.inl, csrc/slposegraph.inl); parity with Open3D is unpinned and
+# tests/posegraph_oracle.py is the restatement the tests check against.
+def get_information_matrix_from_point_clouds(source, target, max_correspondence_distance, transformation, *,
+                                             info: bool = False, device=None):
+    """o3d.pipelines.registration.get_information_matrix_from_point_clouds
+    (source, target, max_correspondence_distance, transformation) on the GPU
+    (sl_information_matrix) -> the 6x6 numpy matrix (with ``info``: also the
+    number of correspondences)."""
+    eng = _engine(device)
+    S = _f64(source, eng.device)
+    T = _f64(target, eng.device)
+    M = np.ascontiguousarray(np.asarray(transformation, dtype=np.float64).reshape(4, 4))
+    out = np.zeros((6, 6))
+    cnt = ctypes.c_int64()
+    _call(eng, "sl_information_matrix", _ptr(S) if len(S) else None, S.shape[0], _ptr(T) if len(T) else None,
+          T.shape[0], float(max_correspondence_distance), M.ctypes.data, out.ctypes.data, ctypes.byref(cnt))
+    return (out, cnt.value) if info else out
+
+
+class PoseGraph:
+    """o3d.pipelines.registration.PoseGraph: ``nodes``, a list of 4x4 poses
+    (node frame -> the frame of node 0), and ``edges``, a list of (source_id,
+    target_id, transformation 4x4 (source -> target), information 6x6,
+    uncertain)."""
+
+    def __init__(self, nodes=None, edges=None):
+        self.nodes = [] if nodes is None else list(nodes)
+        self.edges = [] if edges is None else list(edges)
+
+
+# GlobalOptimizationConvergenceCriteria's defaults
+POSE_GRAPH_CRITERIA = dict(max_iteration=100, min_relative_increment=1e-6, min_relative_residual_increment=1e-6,
+                           min_right_term=1e-6, min_residual=1e-6, max_iteration_lm=20)
+
+
+def global_optimization(pose_graph: PoseGraph, *, max_correspondence_distance, edge_prune_threshold: float = 0.25,
+                        reference_node: int = 0, criteria=None) -> dict:
+    """o3d.pipelines.registration.global_optimization(pose_graph,
+    GlobalOptimizationLevenbergMarquardt(), criteria, GlobalOptimizationOption(
+    max_correspondence_distance, edge_prune_threshold, reference_node))
+    (Old/new360Merge.py:121-131) by sl_pose_graph_optimize: host code of the
+    library, no GPU.  Updates ``pose_graph.nodes`` in place -> {"iterations",
+    "initial_residual", "final_residual"} (the sum of e^T Lambda e over the
+    edges).  ``criteria``: a dict overriding POSE_GRAPH_CRITERIA.
+
+    Every edge must be certain, as the reference marks them: the line process
+    and edge pruning are not implemented and an ``uncertain`` edge raises
+    ValueError.  ``max_correspondence_distance`` and ``edge_prune_threshold``
+    only steer those two in Open3D; they are accepted and unused."""
+    unknown = set(criteria or {}) - set(POSE_GRAPH_CRITERIA)
+    if unknown:
+        raise ValueError(f"unknown criteria: {sorted(unknown)}")
+    c = dict(POSE_GRAPH_CRITERIA, **(criteria or {}))
+    n, m = len(pose_graph.nodes), len(pose_graph.edges)
+    if any(e[4] for e in pose_graph.edges):
+        raise ValueError("global_optimization: an edge is marked uncertain; the line process and edge pruning are "
+                         "not implemented (every edge must be certain)")
+    poses = np.ascontiguousarray(np.asarray(pose_graph.nodes, dtype=np.float64).reshape(n, 16))
+    src = np.ascontiguousarray([e[0] for e in pose_graph.edges], dtype=np.int32)
+    tgt = np.ascontiguousarray([e[1] for e in pose_graph.edges], dtype=np.int32)
+    X = np.ascontiguousarray(np.asarray([e[2] for e in pose_graph.edges], dtype=np.float64).reshape(m, 16))
+    L = np.ascontiguousarray(np.asarray([e[3] for e in pose_graph.edges], dtype=np.float64).reshape(m, 36))
+    it, r0, r1 = ctypes.c_int(), ctypes.c_double(), ctypes.c_double()
+    code = _lib.load().sl_pose_graph_optimize(
+        poses.ctypes.data, n, src.ctypes.data, tgt.ctypes.data, X.ctypes.data, L.ctypes.data, None, m,
+        int(reference_node), int(c["max_iteration"]), int(c["max_iteration_lm"]), float(c["min_right_term"]),
+        float(c["min_relative_increment"]), float(c["min_relative_residual_increment"]), float(c["min_residual"]),
+        ctypes.byref(it), ctypes.byref(r0), ctypes.byref(r1))
+    _lib.check(code, None, f"sl_pose_graph_optimize: {n} nodes, reference node {reference_node}: no node, a "
+                           "reference node or an edge id out of range, or bad criteria")
+    pose_graph.nodes[:] = [poses[i].reshape(4, 4).copy() for i in range(n)]
+    return {"iterations": it.value, "initial_residual": r0.value, "final_residual": r1.value}
+
+
+def full_registration(views, voxel_size: float, *, seed_poses=None, ransac_seed: int = 0, max_iteration: int = 30,
+                      device=None) -> PoseGraph:
+    """load_point_clouds' features and full_registration's loop
+    (Old/new360Merge.py:37-62, 96-119) over ``views`` (clouds, [N, 3] each) ->
+    the PoseGraph before optimisation.  Per view: normals of the full cloud
+    (radius 2 voxel, max_nn 30), then preprocess_point_cloud.  For every pair
+    (i, i + 1), and (0, n - 1) when n > 2, in the reference's order and with
+    the lower id as the source: the global RANSAC estimate on the down-sampled
+    clouds (``ransac_seed`` + the edge's number fixes its draw), point-to-plane
+    ICP on the FULL clouds at 0.4 voxel from it, and the information matrix at
+    0.4 voxel with the ICP's result; node k + 1 is the inverse of the
+    accumulated odometry.  With ``seed_poses`` (poses mapping each view into a
+    common frame, as merge_pro_360 takes them) the RANSAC estimate is replaced
+    by ``inverse(seed_poses[t]) @ seed_poses[s]`` and the down-sampled clouds
+    and features, which only RANSAC reads, are not computed."""
+    eng = _engine(device)
+    clouds = [_f64(v, eng.device) for v in views]
+    n = len(clouds)
+    if seed_poses is not None:
+        seed_poses = np.asarray(seed_poses, dtype=np.float64).reshape(-1, 4, 4)
+        if len(seed_poses) != n:
+            raise ValueError(f"{n} clouds but {len(seed_poses)} seed poses")
+    print(f"Found {n} scans. Extracting geometric features...")
+    normals = [estimate_normals(P, voxel_size * 2, 30, device=eng.device) for P in clouds]
+    down = [preprocess_point_cloud(P, voxel_size, device=eng.device) for P in clouds] if seed_poses is None else None
+    graph = PoseGraph([np.eye(4)])
+    odometry = np.eye(4)
+    distance = voxel_size * 0.4
+    for s in range(n):
+        for t in range(s + 1, n):
+            if not (t == s + 1 or (s == 0 and t == n - 1)):
+                continue
+            print(f"\nAligning scan {s} to {t}...")
+            if seed_poses is None:
+                print("  -> Running Global Registration (RANSAC)...")
+                init = execute_global_registration(down[s][0], down[t][0], down[s][2], down[t][2], voxel_size,
+                                                   seed=ransac_seed + len(graph.edges),
+                                                   device=eng.device)["transformation"]
+            else:
+                init = mat4(rigid_inverse(seed_poses[t]), seed_poses[s])
+            print("  -> Running Fine ICP...")
+            T_icp = registration_icp(clouds[s], clouds[t], normals[t], distance, init, max_iteration=max_iteration,
+                                     device=eng.device)["transformation"]
+            information = get_information_matrix_from_point_clouds(clouds[s], clouds[t], distance, T_icp,
+                                                                   device=eng.device)
+            if t == s + 1:
+                odometry = mat4(T_icp, odometry)
+                graph.nodes.append(rigid_inverse(odometry))
+            graph.edges.append((s, t, T_icp, information, False))
+    return graph
+
+
+def merge_360_pose_graph(input_folder, output_path, voxel_size: float = 1.0, *, order: str = "numeric",
+                         seed_poses=None, ransac_seed: int = 0, binary: bool = True, return_graph: bool = False,
+                         device=None):
+    """Old/new360Merge.py:152-178, the loop-closing 360 merge: the clouds of
+    ``input_folder`` (``ply_files(order)``; default the script's numeric order)
+    through ``full_registration``, then ``global_optimization`` (0.4 voxel,
+    0.25, reference node 0), every view moved by its node's pose, the views
+    concatenated, down-sampled at 0.5 voxel, filtered by
+    remove_statistical_outlier(20, 2.0), normals estimated, and written in
+    Open3D's layout (ply.save_ply_open3d).  The script's bare
+    ``estimate_normals()`` is Open3D's default, a 30-nearest-neighbour search;
+    here the normals are merge_pro_360's (radius 2 voxel, max_nn 30).  Returns
+    (points, colors, normals) on the device (+ the optimised PoseGraph with
+    ``return_graph``).  The Poisson mesh the script appends is ``mesh_360`` on
+    the written file."""
+    files = ply_files(input_folder, order)
+    if len(files) < 2:
+        raise ValueError("Need at least 2 .ply files to merge.")
+    eng = _engine(device)
+    pcds = []
+    for f in files:
+        P, C = ply.read_ply(f)
+        pcds.append((torch.from_numpy(np.ascontiguousarray(P, dtype=np.float64)).to(eng.device),
+                     torch.from_numpy(np.ascontiguousarray(C)).to(eng.device)))
+    graph = full_registration([p for p, _ in pcds], voxel_size, seed_poses=seed_poses, ransac_seed=ransac_seed,
+                              device=eng.device)
+    print("\nRunning Pose Graph Optimization...")
+    global_optimization(graph, max_correspondence_distance=voxel_size * 0.4, edge_prune_threshold=0.25,
+                        reference_node=0)
+    print("Transforming points...")
+    parts_p = [transform(p, graph.nodes[i], device=eng.device) for i, (p, _) in enumerate(pcds)]
+    print("\nMerging point clouds...")
+    print("Post-processing (Removing noise)...")
+    P, C = postprocess(torch.cat(parts_p), torch.cat([c for _, c in pcds]), voxel_size * 0.5, 20, 2.0,
+                       device=eng.device)
+    N = estimate_normals(P, voxel_size * 2, 30, device=eng.device)
+    print("Saving merged point cloud...")
+    ply.save_ply_open3d(P.cpu().numpy(), C.cpu().numpy(), output_path, normals=N.cpu().numpy(), binary=binary)
+    print(f"Point cloud saved to {output_path}")
+    return (P, C, N, graph) if return_graph else (P, C, N)

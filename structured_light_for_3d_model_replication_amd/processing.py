@@ -12,7 +12,10 @@ errors, and runs them on the GPU through ``merge`` (libslgpu.so):
 * ``remove_outliers`` (:55-76) -> ``merge.remove_statistical_outlier`` +
   ``merge.select_by_index``.
 * ``preprocess_point_cloud``, ``execute_global_registration`` and
-  ``merge_pro_360`` delegate to ``merge``.
+  ``merge_pro_360`` delegate to ``merge``.  ``merge_360_loop_closure`` is one
+  more method, the reference's full-turn script Old/new360Merge.py
+  (``merge.merge_360_pose_graph``: the closing pair registered too and the
+  pose graph optimised).
 * ``reconstruct_stl`` (:185-249) and ``mesh_360`` (:252-311) -> ``mesh.
   create_from_point_cloud_poisson`` (FFT Poisson reconstruction on a dense
   grid and marching tetrahedra, csrc/slmesh.inl), the density trim and a
@@ -138,6 +141,12 @@ class ProcessingLogic:
     @staticmethod
     def merge_pro_360(input_folder, output_path, voxel_size=0.02):
         merge.merge_pro_360(input_folder, output_path, voxel_size)
+
+    @staticmethod
+    def merge_360_loop_closure(input_folder, output_path, voxel_size=1.0):
+        """The reference's full-turn script (Old/new360Merge.py): neighbouring views and the closing pair
+        registered, the pose graph optimised, the views merged (merge.merge_360_pose_graph)."""
+        merge.merge_360_pose_graph(input_folder, output_path, voxel_size)
 
     @staticmethod
     def _load_for_meshing(input_path):
