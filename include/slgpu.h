@@ -564,6 +564,43 @@ int sl_orient_normals_mst(sl_ctx* ctx, const double* xyz, double* normals, int64
                           void* stream);
 int sl_orient_normals_mst_stats(int* rounds, int* jumps, int capacity);
 
+/* ---- density clustering (Old/StatisticalOutlierRemoval.py: remove_outliers_keep_color2) ----
+ * compute_nearest_neighbor_distance, cluster_dbscan and remove_radius_outlier
+ * restated (csrc/slcluster.inl; tests/cluster_oracle.py is the CPU restatement,
+ * exact; parity with Open3D unpinned).  xyz [n][3]: device f64.
+ *   neighbourhood  j is a neighbour of i iff ((dx dx + dy dy) + dz dz) < r r in
+ *                  f64, uncontracted, in that order; i itself is one.
+ * sl_radius_count: min(neighbour count, cap) of every point -> out_cnt [n]
+ * (device int32); cap <= 0: the exact count.  remove_radius_outlier(nb_points,
+ * radius) keeps the points with a count > nb_points (cap nb_points + 1).
+ * sl_cluster_dbscan: PointCloud::ClusterDBSCAN's labels in their order-free
+ * form -> labels [n] (device int32), the number of clusters -> *n_clusters
+ * (host, may be NULL):
+ *   core     neighbour count >= min_points;
+ *   cluster  a connected component of the core points (edges: neighbours);
+ *   label    the rank of the cluster's smallest core index among the clusters'
+ *            smallest core indices, 0, 1, 2, ...;
+ *   border   a non-core point with a core neighbour: the smallest label among
+ *            its core neighbours' clusters;
+ *   noise    a non-core point without a core neighbour: -1.
+ * Lock-free union-find on the device (roots hooked under smaller roots by
+ * compare-and-swap); nothing spins and the host iterates nothing.  Scratch: the
+ * search grid + 28 n bytes.  sl_cluster_dbscan_stats: the calling thread's last
+ * call's host milliseconds per stage (grid, count, union, flatten + rank,
+ * border; stage_ms[capacity], zero-filled) -- a measurement aid.
+ * sl_nearest_neighbor_distance: the distance to the nearest other point (the
+ * second entry of the exact 2-NN, ties by (d2, index): a duplicated point gives
+ * 0) -> out [n] (device f64); 0 for n == 1.
+ * All: n == 0 succeeds and writes nothing.  SL_EINVAL with a message: NULL
+ * arguments, n >= 2^31, non-finite coordinates, radius / eps <= 0 or not
+ * finite, min_points < 1.  Blocking on `stream`. */
+int sl_radius_count(sl_ctx* ctx, const double* xyz, int64_t n, double radius, int cap, int32_t* out_cnt,
+                    void* stream);
+int sl_cluster_dbscan(sl_ctx* ctx, const double* xyz, int64_t n, double eps, int min_points, int32_t* labels,
+                      int64_t* n_clusters, void* stream);
+int sl_cluster_dbscan_stats(double* stage_ms, int capacity);
+int sl_nearest_neighbor_distance(sl_ctx* ctx, const double* xyz, int64_t n, double* out, void* stream);
+
 /* Release the scratch buffers the merge entry points keep pooled for `device`
  * (kept otherwise for the process's lifetime, at most 16 GiB per device);
  * the bytes released -> *released_bytes (may be NULL). */

@@ -41,6 +41,7 @@ EXPORTS = ("sl_abi_version", "sl_ctx_create", "sl_ctx_destroy", "sl_ctx_last_err
            "sl_orient_normals", "sl_mesh_extract_count", "sl_mesh_extract_emit", "sl_mesh_remove_vertices",
            "sl_orient_normals_mst", "sl_orient_normals_mst_stats",
            "sl_information_matrix", "sl_pose_graph_optimize",
+           "sl_radius_count", "sl_cluster_dbscan", "sl_cluster_dbscan_stats", "sl_nearest_neighbor_distance",
            "sl_decode_triangulate_batch", "sl_last_error")
 
 _vp = ctypes.c_void_p
@@ -118,6 +119,10 @@ _SIGS = {
     "sl_pose_graph_optimize": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, ctypes.c_double,
                                        ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.POINTER(_i32),
                                        ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
+    "sl_radius_count": (_i32, [_vp, _vp, _i64, ctypes.c_double, _i32, _vp, _vp]),
+    "sl_cluster_dbscan": (_i32, [_vp, _vp, _i64, ctypes.c_double, _i32, _vp, ctypes.POINTER(_i64), _vp]),
+    "sl_cluster_dbscan_stats": (_i32, [ctypes.POINTER(ctypes.c_double), _i32]),
+    "sl_nearest_neighbor_distance": (_i32, [_vp, _vp, _i64, _vp, _vp]),
     "sl_gather_unique_id": (_i32, [_vp]),
     "sl_gather_init": (_i32, [_vp, _i32, _i32, _vp]),
     "sl_gather_counts": (_i32, [_vp, _i64, _vp, _vp]),

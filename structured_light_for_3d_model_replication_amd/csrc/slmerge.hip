@@ -1652,19 +1652,27 @@ int sl_voxel_downsample(sl_ctx* c, const double* xyz, const uint8_t* bgr, int64_
   return SL_OK;
 }
 
-int sl_statistical_outliers(sl_ctx* c, const double* xyz, int64_t n, int nb_neighbors, double std_ratio,
-                            double* avg_dist, int64_t* out_index, int64_t* out_n, void* stream) {
-  if (!c || !out_n || n < 0 || (n && (!xyz || !avg_dist || !out_index))) return SL_EINVAL;
-  if (nb_neighbors < 1 || !(std_ratio > 0.0))
-    return slgpu_fail(c, SL_EINVAL, "Illegal input parameters, number of neighbors and standard deviation ratio "
-                                    "must be positive");
-  if (nb_neighbors > kMaxK) return slgpu_fail(c, SL_EINVAL, "nb_neighbors > 32 is not supported");
-  if (n >= (1ll << 31)) return slgpu_fail(c, SL_EINVAL, "at most 2^31 - 1 points");
-  *out_n = 0;
-  if (n == 0) return SL_OK;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  PoolStream pool_stream(s);
-  MTRY(c, hipSetDevice(slgpu_device(c)));
+}  // extern "C"
+
+namespace {
+
+// One launch of a kNN kernel template with the register list length `km`: 20
+// (the common nb_neighbors), 2 (the nearest-neighbour distance) or kMaxK.
+#define KNN_LAUNCH(kernel, km, grid, block, s, ...)                                         \
+  do {                                                                                      \
+    if ((km) == 20) hipLaunchKernelGGL(kernel<20>, grid, block, 0, s, __VA_ARGS__);         \
+    else if ((km) == 2) hipLaunchKernelGGL(kernel<2>, grid, block, 0, s, __VA_ARGS__);      \
+    else hipLaunchKernelGGL(kernel<kMaxK>, grid, block, 0, s, __VA_ARGS__);                 \
+  } while (0)
+
+// The exact kNN pass of sl_statistical_outliers (and, with k = 2, of
+// sl_nearest_neighbor_distance): the mean of the square roots of the
+// nb_neighbors smallest squared distances of every point (itself included, so
+// min(nb_neighbors, n) of them), in ascending order -> avg_dist [n] (device).
+// km: the kernels' register list length, nb_neighbors itself (20 or 2) or
+// kMaxK.  n >= 1; the caller holds the PoolStream and has set the device.
+int knn_mean_dist(sl_ctx* c, const double* xyz, int64_t n, int nb_neighbors, int km, double* avg_dist,
+                  hipStream_t s) {
   double b[6];
   int r = bounds(c, xyz, n, b, s);
   if (r) return r;
@@ -1774,11 +1782,7 @@ int sl_statistical_outliers(sl_ctx* c, const double* xyz, int64_t n, int nb_neig
   MTRY(c, hipMemsetAsync(slow_n.p, 0, sizeof(unsigned), s));
   py.slow_q = slow_q.p;
   py.slow_n = slow_n.p;
-  if (nb_neighbors == 20)
-    hipLaunchKernelGGL(k_knn_mean<20>, dim3(blocks(n)), dim3(kT), 0, s, xyz, n, idx.p, py, nb_neighbors, avg_dist);
-  else
-    hipLaunchKernelGGL(k_knn_mean<kMaxK>, dim3(blocks(n)), dim3(kT), 0, s, xyz, n, idx.p, py, nb_neighbors,
-                       avg_dist);
+  KNN_LAUNCH(k_knn_mean, km, dim3(blocks(n)), dim3(kT), s, xyz, n, idx.p, py, nb_neighbors, avg_dist);
   MTRY(c, hipGetLastError());
   unsigned n_slow = 0;
   MTRY(c, hipMemcpyAsync(&n_slow, slow_n.p, sizeof(unsigned), hipMemcpyDeviceToHost, s));
@@ -1793,12 +1797,8 @@ int sl_statistical_outliers(sl_ctx* c, const double* xyz, int64_t n, int nb_neig
       MTRY(c, over_q.alloc(n_slow));
       MTRY(c, over_n.alloc(1));
       MTRY(c, hipMemsetAsync(over_n.p, 0, sizeof(unsigned), s));
-      if (nb_neighbors == 20)
-        hipLaunchKernelGGL(k_knn_best<20>, dim3(n_slow), dim3(64), 0, s, idx.p, n, py, nb_neighbors, avg_dist,
-                           over_q.p, over_n.p);
-      else
-        hipLaunchKernelGGL(k_knn_best<kMaxK>, dim3(n_slow), dim3(64), 0, s, idx.p, n, py, nb_neighbors, avg_dist,
-                           over_q.p, over_n.p);
+      KNN_LAUNCH(k_knn_best, km, dim3(n_slow), dim3(64), s, idx.p, n, py, nb_neighbors, avg_dist, over_q.p,
+                 over_n.p);
       MTRY(c, hipGetLastError());
       MTRY(c, hipMemcpyAsync(&n_over, over_n.p, sizeof(unsigned), hipMemcpyDeviceToHost, s));
       MTRY(c, hipStreamSynchronize(s));
@@ -1806,10 +1806,7 @@ int sl_statistical_outliers(sl_ctx* c, const double* xyz, int64_t n, int nb_neig
     if (n_over) {
       Pyramid pq = py;
       if (!climb_only) pq.slow_q = over_q.p;
-      if (nb_neighbors == 20)
-        hipLaunchKernelGGL(k_knn_slow<20>, dim3(n_over), dim3(64), 0, s, idx.p, n, pq, nb_neighbors, avg_dist);
-      else
-        hipLaunchKernelGGL(k_knn_slow<kMaxK>, dim3(n_over), dim3(64), 0, s, idx.p, n, pq, nb_neighbors, avg_dist);
+      KNN_LAUNCH(k_knn_slow, km, dim3(n_over), dim3(64), s, idx.p, n, pq, nb_neighbors, avg_dist);
       MTRY(c, hipGetLastError());
     }
     if (getenv("SLGPU_MERGE_STATS")) fprintf(stderr, "[slmerge] slow=%u overflow=%u\n", n_slow, climb_only ? 0u : n_over);
@@ -1823,6 +1820,33 @@ int sl_statistical_outliers(sl_ctx* c, const double* xyz, int64_t n, int nb_neig
     for (int l = 0; l < py.levels; ++l) fprintf(stderr, " %u", h[kMaxLevels + l]);
     fprintf(stderr, "\n");
   }
+  return SL_OK;
+}
+
+#undef KNN_LAUNCH
+
+}  // namespace
+
+extern "C" {
+
+int sl_statistical_outliers(sl_ctx* c, const double* xyz, int64_t n, int nb_neighbors, double std_ratio,
+                            double* avg_dist, int64_t* out_index, int64_t* out_n, void* stream) {
+  if (!c || !out_n || n < 0 || (n && (!xyz || !avg_dist || !out_index))) return SL_EINVAL;
+  if (nb_neighbors < 1 || !(std_ratio > 0.0))
+    return slgpu_fail(c, SL_EINVAL, "Illegal input parameters, number of neighbors and standard deviation ratio "
+                                    "must be positive");
+  if (nb_neighbors > kMaxK) return slgpu_fail(c, SL_EINVAL, "nb_neighbors > 32 is not supported");
+  if (n >= (1ll << 31)) return slgpu_fail(c, SL_EINVAL, "at most 2^31 - 1 points");
+  *out_n = 0;
+  if (n == 0) return SL_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  PoolStream pool_stream(s);
+  MTRY(c, hipSetDevice(slgpu_device(c)));
+  int r = knn_mean_dist(c, xyz, n, nb_neighbors, nb_neighbors == 20 ? 20 : kMaxK, avg_dist, s);
+  if (r) return r;
+  DBuf<uint32_t> flag, seg;
+  MTRY(c, flag.alloc(n));
+  MTRY(c, seg.alloc(n));
   // cloud mean / std of the positive means: sequential, as std::accumulate /
   // std::inner_product in RemoveStatisticalOutliers.  The means stream to the
   // host through two pinned 1 MB buffers, the copy of one chunk overlapping
@@ -2155,3 +2179,5 @@ int sl_merge_pool_trim(int device, int64_t* released_bytes) {
 // loop-closing 360 merge: the edges' information matrices (GPU) and the pose-graph optimiser (host only)
 #include "slinfo.inl"
 #include "slposegraph.inl"
+// density clustering of the per-view clean-up: radius counts, DBSCAN, nearest-neighbour distance
+#include "slcluster.inl"

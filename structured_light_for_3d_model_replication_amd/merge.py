@@ -172,6 +172,104 @@ def segment_plane(points, distance_threshold, ransac_n: int = 3, num_iterations:
     return plane, inl[: k.value], {"iterations": it.value, "rest": rest[: n - k.value]}
 
 
+# ---------------------------------------------------- density clustering ----
+# Old/StatisticalOutlierRemoval.py's second recipe (remove_outliers_keep_color2):
+# compute_nearest_neighbor_distance, keep_largest_cluster(cluster_dbscan) and
+# remove_radius_outlier.  Open3D's algorithms restated (csrc/slcluster.inl);
+# parity with Open3D is unpinned and tests/cluster_oracle.py is the restatement
+# the tests check against, exactly.  A neighbour of i is a point with
+# ((dx dx + dy dy) + dz dz) < r r (f64, in that order), i itself included.
+def radius_count(points, radius: float, cap: int = 0, *, device=None) -> torch.Tensor:
+    """min(neighbour count within ``radius``, ``cap``) of every point
+    (sl_radius_count; ``cap <= 0``: the exact count) -> int32 [N] on the device."""
+    eng = _engine(device)
+    P = _f64(points, eng.device)
+    n = P.shape[0]
+    cnt = torch.empty(max(n, 1), dtype=torch.int32, device=eng.device)
+    _call(eng, "sl_radius_count", _ptr(P) if n else None, n, float(radius), int(cap), cnt.data_ptr())
+    return cnt[:n]
+
+
+def cluster_dbscan(points, eps: float, min_points: int, *, device=None, info: bool = False):
+    """PointCloud.cluster_dbscan(eps, min_points) (sl_cluster_dbscan) -> labels
+    int32 [N] on the device: -1 noise, else the cluster, numbered by its
+    smallest core index; a border point takes the smallest label among its core
+    neighbours' clusters.  With ``info``: also {"clusters", "core", "noise"}
+    (the core points are counted by one more capped radius_count)."""
+    eng = _engine(device)
+    P = _f64(points, eng.device)
+    n = P.shape[0]
+    labels = torch.empty(max(n, 1), dtype=torch.int32, device=eng.device)
+    k = ctypes.c_int64()
+    _call(eng, "sl_cluster_dbscan", _ptr(P) if n else None, n, float(eps), int(min_points), labels.data_ptr(),
+          ctypes.byref(k))
+    labels = labels[:n]
+    if not info:
+        return labels
+    core = int((radius_count(P, eps, min_points, device=eng.device) >= int(min_points)).sum()) if n else 0
+    return labels, {"clusters": k.value, "core": core, "noise": int((labels < 0).sum())}
+
+
+def remove_radius_outlier(points, nb_points: int, radius: float, *, device=None) -> torch.Tensor:
+    """PointCloud.remove_radius_outlier(nb_points, radius) -> the indices
+    (int64, ascending, on the device) of the points with more than ``nb_points``
+    neighbours within ``radius``, themselves included; pass them to
+    ``select_by_index``."""
+    if nb_points < 1 or not radius > 0:
+        raise ValueError("Illegal input parameters, number of points and radius must be positive")
+    cnt = radius_count(points, radius, int(nb_points) + 1, device=device)
+    return torch.nonzero(cnt > int(nb_points)).reshape(-1)
+
+
+def compute_nearest_neighbor_distance(points, *, device=None) -> torch.Tensor:
+    """PointCloud.compute_nearest_neighbor_distance() (sl_nearest_neighbor_
+    distance) -> f64 [N] on the device: the distance to the nearest other point
+    (0 for a duplicated point and for a cloud of one point)."""
+    eng = _engine(device)
+    P = _f64(points, eng.device)
+    n = P.shape[0]
+    out = torch.empty(max(n, 1), dtype=torch.float64, device=eng.device)
+    _call(eng, "sl_nearest_neighbor_distance", _ptr(P) if n else None, n, out.data_ptr())
+    return out[:n]
+
+
+def largest_cluster_label(labels) -> int | None:
+    """The label >= 0 with the most points, the lowest on equal counts (np.unique
+    sorts and ``counts.argmax()`` takes the first); None when there is none.
+    The histogram and its first maximum are computed where ``labels`` lives."""
+    L = torch.as_tensor(labels)
+    L = L[L >= 0].to(torch.int64)
+    if L.numel() == 0:
+        return None
+    counts = torch.bincount(L)
+    return int(torch.nonzero(counts == counts.max()).reshape(-1)[0])  # the first index equal to the max
+
+
+def keep_largest_cluster(points, colors=None, eps: float = 5, min_points: int = 200, *, device=None):
+    """keep_largest_cluster (Old/StatisticalOutlierRemoval.py:5-32): the points
+    of cluster_dbscan's most populous cluster -> (points, colors | None) on the
+    device; an empty cloud, or one that is all noise, comes back unchanged."""
+    eng = _engine(device)
+    P = _f64(points, eng.device)
+    C = _u8(colors, eng.device, P.shape[0])
+    if P.shape[0] == 0:
+        return P, C
+    labels = cluster_dbscan(P, eps, min_points, device=eng.device)
+    best = largest_cluster_label(labels)
+    if best is None:
+        return P, C
+    return select_by_index(P, C, torch.nonzero(labels == best).reshape(-1), device=eng.device)
+
+
+def cluster_dbscan_stage_ms(*, device=None) -> dict:
+    """Host milliseconds per stage of this thread's last cluster_dbscan
+    (sl_cluster_dbscan_stats; a measurement aid)."""
+    eng = _engine(device)
+    ms = (ctypes.c_double * 5)()
+    _lib.check(eng._L.sl_cluster_dbscan_stats(ms, 5), None, "sl_cluster_dbscan_stats")
+    return dict(zip(("grid", "count", "union", "rank", "border"), ms))
+
+
 def transform(points, pose, *, device=None) -> torch.Tensor:
     """PointCloud.transform(pose) on a device copy of points (row order ((m0 x + m1 y) + m2 z) + m3)."""
     eng = _engine(device)
