@@ -2,7 +2,13 @@
 tests/plane_oracle.py bit for bit, and the ``processing`` drop-in built on it.
 Open3D is not installed: parity with Open3D is unpinned; the oracle restates
 its SegmentPlane with the two documented deviations (seeded draw that may
-repeat a point; zero plane when nothing ever becomes the best)."""
+repeat a point; zero plane when nothing ever becomes the best).
+
+These scenes stay on one path through slplane.inl.  The others -- batches and
+ties above 256, more than 256 chunks, the det_x / det_y branches of the final
+fit, ransac_n 4 and 16, a fitness of 1, zero iterations, a distance equal to
+the threshold, non-finite points, a full last chunk -- are in
+test_gpu_plane_paths.py, on the inputs of tests/plane_cases.py."""
 import os
 
 import numpy as np
