@@ -78,10 +78,19 @@ def box(points, depth: int, scale: float = 1.1):
     return c - L / 2.0, h, R
 
 
+CELL_MAX = 9.0e18       # a floor at or beyond it (or NaN) is cell 0: every other one is an int64
+
+
 def _cell(P, origin, h):
-    g = (np.asarray(P, dtype=np.float64) - origin) / h
-    fl = np.floor(g)
-    return fl.astype(np.int64), g - fl
+    """corners() of slmesh.inl: fl = floor(g); the cell is int64(fl) where |fl|
+    < 9.0e18, else 0 (NaN too); f = g - fl (NaN for a NaN or infinite g).  The
+    cell is wrapped by the caller's ``& (R - 1)``."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        g = (np.asarray(P, dtype=np.float64) - origin) / h
+        fl = np.floor(g)
+        f = g - fl
+        ok = np.abs(fl) < CELL_MAX
+    return np.where(ok, fl, 0.0).astype(np.int64), f
 
 
 def _corner_weight(f, c):
@@ -99,14 +108,22 @@ def _corner_index(i0, c, R):
 
 
 def _fix(v):
-    t = v * FIX
-    with np.errstate(invalid="ignore"):
+    """fix() of slmesh.inl: |t| < 2^62 ? rint(t) : 0 with t = v 2^30 (so an
+    infinite or NaN t adds 0); no operation here warns on such a t."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        t = np.asarray(v, dtype=np.float64) * FIX
         ok = np.abs(t) < FIX_MAX
-    return np.where(ok, np.rint(np.where(ok, t, 0.0)), 0.0).astype(np.int64)
+    return np.rint(np.where(ok, t, 0.0)).astype(np.int64)
 
 
 def splat(points, normals, origin, h, R):
     """-> (W f32 [R,R,R], V f32 [3,R,R,R]): 64-bit fixed-point sums."""
+    G = unfix(splat_sums(points, normals, origin, h, R)).reshape(4, R, R, R)
+    return G[0], G[1:]
+
+
+def splat_sums(points, normals, origin, h, R):
+    """The splat's accumulators -> int64 [4, R^3] (W, V_x, V_y, V_z); the sums wrap."""
     N = np.asarray(normals, dtype=np.float64)
     i0, f = _cell(points, origin, h)
     acc = np.zeros((4, R * R * R), dtype=np.int64)
@@ -115,19 +132,26 @@ def splat(points, normals, origin, h, R):
         lin = _corner_index(i0, c, R)
         np.add.at(acc[0], lin, _fix(w))
         for a in range(3):
-            np.add.at(acc[1 + a], lin, _fix(w * N[:, a]))
-    G = (acc.astype(np.float64) * (1.0 / FIX)).astype(np.float32).reshape(4, R, R, R)
-    return G[0], G[1:]
+            with np.errstate(invalid="ignore", over="ignore"):  # 0 inf, and a NaN weight: fix gives 0
+                wn = w * N[:, a]
+            np.add.at(acc[1 + a], lin, _fix(wn))
+    return acc
+
+
+def unfix(acc):
+    """float(double(sum) 2^-30) of every accumulator."""
+    return (np.asarray(acc, dtype=np.int64).astype(np.float64) * (1.0 / FIX)).astype(np.float32)
 
 
 def divergence(V, h):
     V = np.asarray(V, dtype=np.float32)
-    dx = np.roll(V[0], -1, 0) - np.roll(V[0], 1, 0)
-    dy = np.roll(V[1], -1, 1) - np.roll(V[1], 1, 1)
-    dz = np.roll(V[2], -1, 2) - np.roll(V[2], 1, 2)
-    s = (dx + dy) + dz
-    assert s.dtype == np.float32
-    return (s.astype(np.float64) / (2.0 * h)).astype(np.float32)
+    with np.errstate(invalid="ignore", over="ignore"):  # inf - inf is NaN, as on the device
+        dx = np.roll(V[0], -1, 0) - np.roll(V[0], 1, 0)
+        dy = np.roll(V[1], -1, 1) - np.roll(V[1], 1, 1)
+        dz = np.roll(V[2], -1, 2) - np.roll(V[2], 1, 2)
+        s = (dx + dy) + dz
+        assert s.dtype == np.float32
+        return (s.astype(np.float64) / (2.0 * h)).astype(np.float32)
 
 
 def eigenvalues(R, h, dtype=np.float64):
@@ -154,8 +178,9 @@ def sample(grid, points, origin, h):
     flat = G.reshape(-1).astype(np.float64)
     i0, f = _cell(points, origin, h)
     acc = np.zeros(len(i0))
-    for c in range(8):
-        acc = acc + _corner_weight(f, c) * flat[_corner_index(i0, c, R)]
+    with np.errstate(invalid="ignore"):  # 0 inf and inf - inf are NaN, as on the device
+        for c in range(8):
+            acc = acc + _corner_weight(f, c) * flat[_corner_index(i0, c, R)]
     return acc
 
 
@@ -198,8 +223,9 @@ def extract(chi, iso, origin, h):
     chi = np.asarray(chi, dtype=np.float32)
     R = chi.shape[0]
     origin = np.asarray(origin, dtype=np.float64)
-    v = chi.astype(np.float64) - float(iso)
-    inside = v < 0.0
+    with np.errstate(invalid="ignore"):  # inf - inf (an infinite iso) is NaN: outside
+        v = chi.astype(np.float64) - float(iso)
+        inside = v < 0.0
     n3 = R * R * R
     crossed = np.zeros((n3, 7), dtype=bool)
     for d in range(1, 8):
@@ -217,8 +243,9 @@ def extract(chi, iso, origin, h):
     nb = ((((i + ((dm1 + 1) & 1)) & (R - 1)) * R + ((j + (((dm1 + 1) >> 1) & 1)) & (R - 1))) * R
           + ((k + (((dm1 + 1) >> 2) & 1)) & (R - 1)))
     vb = v.reshape(-1)[nb]
-    t = va / (va - vb)
-    verts = pa + (pb - pa) * t[:, None]
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):  # a NaN or infinite node: NaN vertices
+        t = va / (va - vb)
+        verts = pa + (pb - pa) * t[:, None]
 
     corner_in = [_shift(inside, c).reshape(-1) for c in range(8)]
     lin = np.arange(n3).reshape(R, R, R)
@@ -251,6 +278,19 @@ def tet_cases(chi, iso):
     return seen
 
 
+def tet_pairs(chi, iso):
+    """The set of (tetrahedron q, case m), q = 0..5, m = 1..14, a field produces
+    (84 at the most: the winding swap of t1, t2, t5 is per tetrahedron)."""
+    with np.errstate(invalid="ignore"):
+        inside = (np.asarray(chi, dtype=np.float32).astype(np.float64) - float(iso)) < 0.0
+    corner_in = [_shift(inside, c).reshape(-1) for c in range(8)]
+    seen = set()
+    for q, corners in enumerate(TET_CORNERS):
+        m = np.unique(sum(corner_in[corners[r]].astype(np.int64) << r for r in range(4)))
+        seen |= {(q, int(x)) for x in m if 0 < x < 15}
+    return seen
+
+
 def lerp_quantile(sorted_lo: float, sorted_hi: float, gamma: float) -> float:
     """numpy.quantile's linear interpolation between the two sorted neighbours."""
     a, b, t = float(sorted_lo), float(sorted_hi), float(gamma)
@@ -267,12 +307,17 @@ def quantile(values, q: float) -> float:
 
 
 def remove_vertices_by_mask(vertices, triangles, mask):
-    mask = np.asarray(mask, dtype=bool)
+    """A triangle with an index outside 0 .. len(vertices) - 1 is dropped; such
+    an index is never used to index anything."""
+    mask = np.asarray(mask, dtype=bool).reshape(-1)
     keep = ~mask
     new = np.cumsum(keep) - keep
-    T = np.asarray(triangles)
-    tk = keep[T].all(1) if len(T) else np.zeros(0, dtype=bool)
-    return np.asarray(vertices)[keep], new[T[tk]].astype(np.int32).reshape(-1, 3)
+    T = np.asarray(triangles, dtype=np.int64).reshape(-1, 3)
+    inside = (T >= 0) & (T < len(keep))
+    tk = np.zeros(len(T), dtype=bool)
+    if len(keep):
+        tk = (inside & keep[np.where(inside, T, 0)]).all(1)
+    return np.asarray(vertices).reshape(-1, 3)[keep], new[T[tk]].astype(np.int32).reshape(-1, 3)
 
 
 def poisson(points, normals, depth, scale=1.1, chi=None):

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import mesh_cases as mc
 from tests import mesh_oracle as mo
 
 pytestmark = pytest.mark.gpu
@@ -44,32 +45,10 @@ def field32(ms, ball):
     return out
 
 
-def _cloud(kind, n, R, seed):
-    """-> (points, normals, scale)"""
-    rng = np.random.default_rng(seed)
-    N = rng.normal(size=(n, 3))
-    scale = 1.1
-    if kind == "nodes":  # scale 1 and extents R: h = 1, origin 0, every point on a node
-        P = rng.integers(0, R + 1, size=(n, 3)).astype(np.float64)
-        P[0] = 0.0
-        P[-1] = R  # (n = 1: a single point, the unit box about it)
-        scale = 1.0
-    elif kind == "faces":  # scale 1: the points of the bounding box's faces lie on the grid's seam
-        P = rng.random((n, 3)) * 3.0 - 1.0
-        P[rng.random((n, 3)) < 0.25] = 2.0
-        P[rng.random((n, 3)) < 0.25] = -1.0
-        scale = 1.0
-    elif kind == "onecell":  # two corner points fix the box; the rest share one cell
-        P = 0.4 + 1e-3 * rng.random((n, 3))
-        P[0] = 0.0
-        P[-1] = 1.0
-    else:  # "flat": a zero-extent axis
-        P = rng.random((n, 3))
-        P[:, 1] = 0.25
-    return P, N, scale
+_cloud = mc.cloud  # (kind, n, R, seed) -> (points, normals, scale)
 
 
-@pytest.mark.parametrize("depth", [3, 4])
+@pytest.mark.parametrize("depth", [1, 2, 3, 4])
 @pytest.mark.parametrize("n", [1, 257, 4097])
 @pytest.mark.parametrize("kind", ["nodes", "faces", "onecell", "flat"])
 def test_splat_and_divergence_bits(ms, kind, n, depth):
@@ -115,16 +94,9 @@ def test_iso_bits(ms, ball, depth):
 
 
 def _fields():
-    rng = np.random.default_rng(11)
-    R = 8
-    i, j, k = np.meshgrid(np.arange(R), np.arange(R), np.arange(R), indexing="ij")
-    wrapped = lambda a: np.minimum(a, R - a)  # noqa: E731  (periodic distance to node 0)
-    return {
-        "random": (rng.normal(size=(R, R, R)).astype(np.float32), 0.0),
-        "on_iso": (rng.integers(-1, 2, size=(R, R, R)).astype(np.float32) + 0.5, 0.5),
-        "seam": (np.sqrt(wrapped(i) ** 2 + wrapped(j) ** 2 + wrapped(k) ** 2).astype(np.float32), 2.3),
-        "constant": (np.full((R, R, R), 0.25, np.float32), 0.25),
-    }
+    """The R = 8 fields of tests/mesh_cases.py (default_rng(11)), writable."""
+    f = mc.fields()
+    return {name: (f[name][0].copy(), f[name][1]) for name in ("random", "on_iso", "seam", "constant")}
 
 
 def _same_mesh(ms, chi, iso, origin, h):
@@ -142,8 +114,11 @@ def test_extraction_bits(ms, name):
     V, T = _same_mesh(ms, chi, iso, np.array([0.3, -1.7, 2.9]), 0.37)
     if name == "random":
         assert set(range(1, 15)) <= mo.tet_cases(chi, iso)
+        assert len(mo.tet_pairs(chi, iso)) == 84  # each case in each tetrahedron (the winding swap is per tetrahedron)
     if name == "on_iso":
         assert (chi == np.float32(iso)).sum() > 100
+    if name in ("random", "on_iso"):
+        assert mo.edge_census(T)[0] and len(T) > 0
     if name == "seam":  # a closed ball about node 0: its vertices reach past node R - 1 on every axis
         assert mo.edge_census(T)[0] and len(T) > 0
         assert (V.max(0) > np.array([0.3, -1.7, 2.9]) + 0.37 * 7).all()
