@@ -601,6 +601,33 @@ int sl_cluster_dbscan(sl_ctx* ctx, const double* xyz, int64_t n, double eps, int
 int sl_cluster_dbscan_stats(double* stage_ms, int capacity);
 int sl_nearest_neighbor_distance(sl_ctx* ctx, const double* xyz, int64_t n, double* out, void* stream);
 
+/* ---- ball-pivoting surface meshing (csrc/slbpa.inl) ----
+ * The reference's reconstruct_stl(mode="surface") (server/processing.py:220-237)
+ * is Open3D's create_from_point_cloud_ball_pivoting, restated in an order-free
+ * form (slbpa.inl states the rules; tests/bpa_oracle.py is their CPU form).
+ * sl_ball_pivot_candidates: the triangles (i, j, k) of the cloud that have an
+ * empty ball of `radius` on the side of their three normals, among the points
+ * that are not inner (vclass u8 [n]: 0 orphan, 1 border, 2 inner; NULL: all
+ * orphans) -> triangles int32 [capacity][3] (device), wound so that the face
+ * normal is on the ball's side, in the lexicographic order of their sorted
+ * triples (two runs write identical arrays), and *count (host).  When *count
+ * exceeds `capacity` nothing is written: call again with capacity >= *count.
+ * A point with more than sl_ball_pivot_max_neighbours() points within twice
+ * the radius (itself included) is SL_EINVAL with a message naming the count
+ * and the limit; a neighbourhood is never truncated.  n == 0 succeeds.
+ * SL_EINVAL with a message: NULL arguments, n >= 2^31, non-finite coordinates,
+ * a radius that is not finite and positive.  Blocking on `stream`.
+ * sl_ball_pivot_candidates_stats: of this thread's last call, host
+ * milliseconds of the grid, the enumeration and the ordering, then the live
+ * queries, the candidates, the neighbourhood that was too large and the
+ * queries of the kernel's second tier (stats[capacity], zero-filled) -- a
+ * measurement aid. */
+int sl_ball_pivot_max_neighbours(void);
+int sl_ball_pivot_candidates(sl_ctx* ctx, const double* xyz, const double* normals, int64_t n, double radius,
+                             const uint8_t* vclass, int32_t* triangles, int64_t capacity, int64_t* count,
+                             void* stream);
+int sl_ball_pivot_candidates_stats(double* stats, int capacity);
+
 /* Release the scratch buffers the merge entry points keep pooled for `device`
  * (kept otherwise for the process's lifetime, at most 16 GiB per device);
  * the bytes released -> *released_bytes (may be NULL). */

@@ -42,6 +42,7 @@ EXPORTS = ("sl_abi_version", "sl_ctx_create", "sl_ctx_destroy", "sl_ctx_last_err
            "sl_orient_normals_mst", "sl_orient_normals_mst_stats",
            "sl_information_matrix", "sl_pose_graph_optimize",
            "sl_radius_count", "sl_cluster_dbscan", "sl_cluster_dbscan_stats", "sl_nearest_neighbor_distance",
+           "sl_ball_pivot_max_neighbours", "sl_ball_pivot_candidates", "sl_ball_pivot_candidates_stats",
            "sl_decode_triangulate_batch", "sl_last_error")
 
 _vp = ctypes.c_void_p
@@ -123,6 +124,10 @@ _SIGS = {
     "sl_cluster_dbscan": (_i32, [_vp, _vp, _i64, ctypes.c_double, _i32, _vp, ctypes.POINTER(_i64), _vp]),
     "sl_cluster_dbscan_stats": (_i32, [ctypes.POINTER(ctypes.c_double), _i32]),
     "sl_nearest_neighbor_distance": (_i32, [_vp, _vp, _i64, _vp, _vp]),
+    "sl_ball_pivot_max_neighbours": (_i32, []),
+    "sl_ball_pivot_candidates": (_i32, [_vp, _vp, _vp, _i64, ctypes.c_double, _vp, _vp, _i64, ctypes.POINTER(_i64),
+                                         _vp]),
+    "sl_ball_pivot_candidates_stats": (_i32, [ctypes.POINTER(ctypes.c_double), _i32]),
     "sl_gather_unique_id": (_i32, [_vp]),
     "sl_gather_init": (_i32, [_vp, _i32, _i32, _vp]),
     "sl_gather_counts": (_i32, [_vp, _i64, _vp, _vp]),

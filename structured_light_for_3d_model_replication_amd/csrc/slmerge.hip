@@ -2181,3 +2181,5 @@ int sl_merge_pool_trim(int device, int64_t* released_bytes) {
 #include "slposegraph.inl"
 // density clustering of the per-view clean-up: radius counts, DBSCAN, nearest-neighbour distance
 #include "slcluster.inl"
+// ball-pivoting surface meshing: the per-point enumeration of the triangles with an empty ball
+#include "slbpa.inl"

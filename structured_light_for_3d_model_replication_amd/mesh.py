@@ -1,6 +1,7 @@
-"""Poisson meshing on the GPU: the fourth step of the reference's workflow
+"""Meshing on the GPU: the fourth step of the reference's workflow
 (server/processing.py:185-311; ``processing.ProcessingLogic.reconstruct_stl``
-and ``mesh_360`` of this package are the drop-ins built on this module).
+and ``mesh_360`` of this package are the drop-ins built on this module):
+Poisson reconstruction (mode "watertight") and ball pivoting (mode "surface").
 
 ``create_from_point_cloud_poisson`` is Kazhdan's FFT Poisson reconstruction on
 a dense periodic grid of R = 2^depth nodes per axis: a trilinear splat of the
@@ -16,6 +17,15 @@ that: the reference's call restated on the kNN graph alone (a minimum spanning
 forest over 1 - |ni . nj| by Boruvka rounds, csrc/slorient.inl, checked bit for
 bit against tests/orient_oracle.py); the drop-ins use it when asked to
 (``tangent_planes=k``).
+
+``create_from_point_cloud_ball_pivoting`` is the reference's other mode
+(:220-237).  Open3D's ball pivoting is a sequential front; it is restated in an
+order-free form: the triangles with an empty ball of the radius on the side of
+their normals are enumerated per point by a HIP kernel (csrc/slbpa.inl, which
+states the rules; ``ball_pivot_candidates`` is that enumeration alone), and the
+pass bookkeeping -- vertex classes, edge counts, the seed and per-edge rules --
+is torch sorts and searches on the device.  tests/bpa_oracle.py is the CPU
+restatement the result equals exactly; the triangle set is not Open3D's.
 
 Open3D's Poisson is the adaptive-octree variant and is not installed here:
 parity with Open3D is unpinned, and tests/mesh_oracle.py is the CPU restatement
@@ -334,6 +344,187 @@ def create_from_point_cloud_poisson(points, normals, depth: int = 8, scale: floa
     dens = vertex_density(f["W"], verts, f["origin"], f["h"], device=verts.device)
     st.mark("density")
     return verts, tris, dens
+
+
+BPA_MAX_NEIGHBOURS = 1024  # sl_ball_pivot_max_neighbours(): the points within twice the radius of a point
+
+
+def _normals_for(points, normals, dev):
+    P = _f64(points, dev)
+    N = torch.as_tensor(normals)
+    if N.dim() != 2 or tuple(N.shape) != tuple(P.shape):
+        raise ValueError("a normal per point is needed")
+    return P, N.to(device=dev, dtype=torch.float64).contiguous()
+
+
+def _radius(r) -> float:
+    r = float(r)
+    if not (np.isfinite(r) and r > 0.0):
+        raise ValueError("a ball radius must be finite and positive")
+    return r
+
+
+def _bpa_candidates(eng, P, N, radius, cls, capacity):
+    n = P.shape[0]
+    count = ctypes.c_int64()
+    while True:
+        tri = torch.empty((max(capacity, 1), 3), dtype=torch.int32, device=eng.device)
+        _call(eng, "sl_ball_pivot_candidates", _ptr(P) if n else None, _ptr(N) if n else None, n, radius,
+              _ptr(cls), _ptr(tri), capacity, ctypes.byref(count))
+        if count.value <= capacity:
+            return tri[: count.value]
+        capacity = count.value  # the buffer was too small: once more at the exact size
+
+
+def ball_pivot_candidates(points, normals, radius, vclass=None, *, device=None) -> torch.Tensor:
+    """sl_ball_pivot_candidates -> int32 [C, 3] on the device: the triangles of
+    the cloud that have an empty ball of ``radius`` on the side of their three
+    normals (csrc/slbpa.inl states the test), among the points that are not
+    inner (``vclass`` u8 [N]: 0 orphan, 1 border, 2 inner; None: all orphans);
+    wound so that the face normal is on the ball's side, in the lexicographic
+    order of the sorted triples.  A point with more than BPA_MAX_NEIGHBOURS
+    points within twice the radius raises ValueError."""
+    eng = _engine(device)
+    P, N = _normals_for(points, normals, eng.device)
+    radius = _radius(radius)
+    cls = None
+    if vclass is not None:
+        cls = torch.as_tensor(vclass).to(device=eng.device, dtype=torch.uint8).contiguous().reshape(-1)
+        if cls.shape[0] != P.shape[0]:
+            raise ValueError("a class per point is needed")
+    return _bpa_candidates(eng, P, N, radius, cls, 3 * P.shape[0] + 1024)
+
+
+def ball_pivot_stats(*, device=None) -> dict:
+    """Of this thread's last enumeration (sl_ball_pivot_candidates_stats; a
+    measurement aid): host milliseconds per stage, the live queries, the candidates and
+    the queries that went to the kernel's second tier (a neighbourhood above its first capacity)."""
+    eng = _engine(device)
+    v = (ctypes.c_double * 7)()
+    _lib.check(eng._L.sl_ball_pivot_candidates_stats(v, 7), None, "sl_ball_pivot_candidates_stats")
+    return {"grid_ms": v[0], "enumerate_ms": v[1], "order_ms": v[2], "live": int(v[3]), "candidates": int(v[4]),
+            "second_tier": int(v[6])}
+
+
+def _edge_keys(T, n):
+    """int64 [t, 3] -> (the sorted triples, the keys a n + b (a < b) of their three edges)."""
+    S = torch.sort(T.to(torch.int64), 1).values
+    return S, torch.stack([S[:, 0] * n + S[:, 1], S[:, 1] * n + S[:, 2], S[:, 0] * n + S[:, 2]], 1)
+
+
+def _count_in(sorted_keys, keys):
+    return torch.searchsorted(sorted_keys, keys, right=True) - torch.searchsorted(sorted_keys, keys)
+
+
+def _bpa_pass(eng, P, N, radius, M, capacity):
+    """One pass (rules 1-6 of csrc/slbpa.inl) over the mesh M int32 [t, 3] -> (the appended triangles
+    in rank order, the number the per-edge rule dropped).  Everything stays on the device; the host
+    reads the candidate count and one pair of counts."""
+    n, dev = P.shape[0], eng.device
+    cls = None
+    if len(M):
+        Sm, em = _edge_keys(M, n)
+        mk = torch.sort(em.reshape(-1)).values
+        once = (_count_in(mk, mk) == 1).to(torch.int32)
+        on_border = torch.zeros(n, dtype=torch.int32, device=dev)
+        on_border.index_put_((torch.div(mk, n, rounding_mode="floor"),), once, accumulate=True)
+        on_border.index_put_((mk % n,), once, accumulate=True)
+        cls = torch.zeros(n, dtype=torch.uint8, device=dev)
+        cls[M.reshape(-1).to(torch.int64)] = 2
+        cls = torch.where(on_border > 0, torch.ones_like(cls), cls)
+    else:
+        mk = torch.zeros(0, dtype=torch.int64, device=dev)
+    C = _bpa_candidates(eng, P, N, radius, cls, capacity)  # rule 1
+    c = len(C)
+    if c == 0:
+        return C, 0
+    S, ek = _edge_keys(C, n)
+    cm = _count_in(mk, ek)
+    keep = (cm < 2).all(1)  # rule 3
+    if len(M):
+        # rule 2: an edge has at most two triangles in M, so the triple is in one of two slots
+        order = torch.argsort(em[:, 0])
+        m_ij, m_k = em[order, 0].contiguous(), Sm[order, 2]
+        c_ij = ek[:, 0].contiguous()
+        lo = torch.searchsorted(m_ij, c_ij)
+        for d in (0, 1):
+            at = torch.clamp(lo + d, max=len(M) - 1)
+            keep &= ~((m_ij[at] == c_ij) & (m_k[at] == S[:, 2]))
+        orphans = (cls[S] == 0).all(1)
+        keep &= (cm > 0).any(1) | orphans  # rule 4
+    # rule 5: entry 3 rank + slot, stably sorted by edge: by edge, then by rank
+    big = torch.iinfo(torch.int64).max
+    flat = torch.where(keep[:, None], ek, torch.full_like(ek, big)).reshape(-1)
+    sk, order = torch.sort(flat, stable=True)
+    place = torch.arange(3 * c, device=dev) - torch.searchsorted(sk, sk)
+    bad = ((place >= 2 - _count_in(mk, sk)) & (sk != big)).to(torch.int32)
+    hits = torch.zeros(c, dtype=torch.int32, device=dev)
+    hits.index_put_((torch.div(order, 3, rounding_mode="floor"),), bad, accumulate=True)
+    dropped = keep & (hits > 0)
+    keep &= ~dropped
+    n_keep, n_drop = torch.stack([keep.sum(), dropped.sum()]).tolist()
+    first = torch.argsort(keep.to(torch.uint8), descending=True, stable=True)[:n_keep]
+    return C[first], n_drop
+
+
+def create_from_point_cloud_ball_pivoting(points, normals, radii, *, max_passes: int = 8, info: bool = False,
+                                          timings=None, device=None):
+    """TriangleMesh.create_from_point_cloud_ball_pivoting(pcd, radii) ->
+    (vertices f64 [N, 3], triangles int32 [T, 3]) on the device; the vertices
+    are the cloud's points.  Open3D's sequential front is restated in an
+    order-free form (csrc/slbpa.inl states the rules, tests/bpa_oracle.py is
+    their CPU form, which the result equals exactly): a triangle belongs to the
+    surface of radius r iff it has an empty r-ball on the side of its three
+    vertex normals; per radius, passes append such triangles at non-inner
+    vertices -- seeds among orphans, the others along an existing edge -- and a
+    per-edge rule keeps every edge at no more than two triangles, until a pass
+    appends nothing (or ``max_passes``).  Triangles come in pass order, then in
+    the lexicographic order of their sorted triples; two runs give identical
+    arrays.  With ``info`` also {"passes" per radius (the last, empty pass
+    included), "triangles" appended per pass, "dropped" by the per-edge rule
+    per pass, "border_edges", "converged"}; ``timings`` (a dict) receives per
+    pass the radius, the milliseconds and ``ball_pivot_stats`` of its enumeration.
+    Deviations: the triangle set is not Open3D's, which depends on its visiting
+    order.  Inputs that are not in general position (exact lattices with
+    co-spherical quads) are decided by rounding: deterministic, but a quad may
+    be covered by both diagonals.  A point with more than BPA_MAX_NEIGHBOURS
+    points within twice a radius raises ValueError."""
+    eng = _engine(device)
+    P, N = _normals_for(points, normals, eng.device)
+    radii = [_radius(r) for r in radii]
+    if not radii:
+        raise ValueError("at least one ball radius is needed")
+    max_passes = int(max_passes)
+    if max_passes < 1:
+        raise ValueError("max_passes must be at least 1")
+    n = P.shape[0]
+    M = torch.zeros((0, 3), dtype=torch.int32, device=eng.device)
+    out = {"passes": [], "triangles": [], "dropped": [], "border_edges": 0, "converged": True}
+    capacity = 3 * n + 1024
+    for r in radii:
+        passes, done = 0, False
+        while passes < max_passes and not done:
+            st = _Stages(None if timings is None else {}, eng.device)
+            new, dropped = _bpa_pass(eng, P, N, r, M, capacity)
+            passes += 1
+            out["triangles"].append(len(new))
+            out["dropped"].append(dropped)
+            M = torch.cat([M, new])
+            done = len(new) == 0
+            if timings is not None:
+                st.mark("pass")
+                timings.setdefault("radius", []).append(r)
+                timings.setdefault("ms", []).append(st.timings["pass"])
+                for key, v in ball_pivot_stats(device=eng.device).items():  # of the pass's enumeration
+                    timings.setdefault(key, []).append(v)
+        out["passes"].append(passes)
+        out["converged"] = out["converged"] and done
+    if not info:
+        return P, M
+    if len(M):
+        mk = torch.sort(_edge_keys(M, n)[1].reshape(-1)).values
+        out["border_edges"] = int((_count_in(mk, mk) == 1).sum())
+    return P, M, out
 
 
 def _host(a, dtype):

@@ -28,9 +28,16 @@ errors, and runs them on the GPU through ``merge`` (libslgpu.so):
   ``mesh.orient_normals_consistent_tangent_plane(k)`` -- the reference's call,
   restated on the kNN graph of the radius the function estimates normals with
   (csrc/slorient.inl); it stays opt-in until it has run on real scans.
-  ``mode="surface"`` (ball pivoting) raises NotImplementedError; only ``.stl``
-  can be written; a depth whose grids do not fit the device raises
-  MemoryError (depth 10 is the largest).
+  ``mode="surface"`` (ball pivoting, :220-237) raises NotImplementedError
+  unless the keyword-only ``ball_pivoting=True`` is given; then it follows the
+  reference's lines -- ``params["radii"]`` (default "1,2,4") times the mean of
+  ``merge.compute_nearest_neighbor_distance``, the print, every exception of
+  the block re-raised as ValueError("Invalid radii parameters: ...") -- with
+  ``mesh.create_from_point_cloud_ball_pivoting``, Open3D's sequential front
+  restated in an order-free form (csrc/slbpa.inl; the triangle set is not
+  Open3D's, which depends on its visiting order).  It stays opt-in until it has
+  run on real scans.  Only ``.stl`` can be written; a depth whose grids do not
+  fit the device raises MemoryError (depth 10 is the largest).
 
 Without Open3D, "a point cloud object" is a ``Cloud(points, colors)`` of
 device tensors (f64 [N, 3], BGR u8 [N, 3] or None).  It is accepted wherever
@@ -164,7 +171,7 @@ class ProcessingLogic:
 
     @staticmethod
     def reconstruct_stl(input_path, output_path, mode="watertight", params=None, *, budget_bytes=None,
-                        tangent_planes=None):
+                        tangent_planes=None, ball_pivoting=False):
         if not os.path.exists(input_path):
             raise FileNotFoundError(f"Input file not found: {input_path}")
         params = {} if params is None else params
@@ -189,7 +196,20 @@ class ProcessingLogic:
             if len(V):
                 V, T = mesh.trim_by_density(V, T, densities, 0.02, device=P.device)
         elif mode == "surface":
-            raise NotImplementedError("mode 'surface' (ball pivoting) is not provided; use mode='watertight'")
+            if not ball_pivoting:
+                raise NotImplementedError("mode 'surface' (ball pivoting) is not provided by default; pass "
+                                          "ball_pivoting=True for its order-free restatement, or use "
+                                          "mode='watertight'")
+            radii_str = params.get("radii", "1,2,4")
+            try:
+                distances = merge.compute_nearest_neighbor_distance(P, device=P.device)
+                avg_dist = mesh.ordered_sum(distances, device=P.device) / float(len(distances))
+                multipliers = [float(x) for x in radii_str.split(',')]
+                radii = [avg_dist * m for m in multipliers]
+                print(f"[Recon] Ball Pivoting (radii={radii})...")
+                V, T = mesh.create_from_point_cloud_ball_pivoting(P, N, radii, device=P.device)
+            except Exception as e:  # noqa: BLE001  (the reference's block catches everything)
+                raise ValueError(f"Invalid radii parameters: {e}")
         else:
             raise ValueError(f"Unknown mode: {mode}")
         if len(V) == 0:
