@@ -273,6 +273,64 @@ int sl_write_ply_device(sl_ctx* ctx, const char* path, const void* xyz, int xyz_
 int sl_write_ply_binary(const char* path, const void* xyz, int xyz_dtype, const uint8_t* bgr, int64_t n,
                         int threads);
 
+/* ---- PLY reader: the body of a vertex-only PLY parsed on the device ----
+ * (csrc/slplyread.inl; the header is the caller's: ply.read_cloud_device) */
+
+/* *status of sl_parse_ply_ascii: accepted, or which condition sends the whole
+ * file to the host reader */
+#define SL_PLY_ACCEPTED 0
+#define SL_PLY_BAD_BYTE 1           /* a byte outside 0-9 + - . e E ' ' \t \r \n ("nan", "inf", '#') */
+#define SL_PLY_BAD_TOKEN 2          /* a token outside the grammar ("1e", "1.2.3")                   */
+#define SL_PLY_TOKEN_COUNT 3        /* not n_rows x n_cols tokens                                     */
+#define SL_PLY_RAGGED_LINE 4        /* a non-blank line without exactly n_cols tokens                 */
+#define SL_PLY_COLOUR_RANGE 5       /* a colour that is no integer in 0..255 (set by the caller, who
+                                       knows which columns are colours)                               */
+#define SL_PLY_UNDECIDED_OVERFLOW 6 /* more undecided tokens than undecided_cap                       */
+
+/* col_type of sl_unpack_ply_binary */
+#define SL_PLY_F32 0
+#define SL_PLY_F64 1
+#define SL_PLY_U8 2
+#define SL_PLY_I8 3
+#define SL_PLY_I16 4
+#define SL_PLY_U16 5
+#define SL_PLY_I32 6
+#define SL_PLY_U32 7
+
+/* The ASCII body (n_bytes at body_dev, device memory, 16-byte aligned) of
+ * n_rows vertices with n_cols properties into table_dev, f64 [n_rows][n_cols],
+ * every token converted as strtod / Python's float() converts it (correctly
+ * rounded), bit for bit.
+ * Tokens are separated by ' ' \t \r \n (as rply reads them).  Grammar:
+ * [+-]? digits [. digits]? ([eE] [+-]? digits)? with a digit in the mantissa
+ * ("5." and ".5" are inside).  A token is +-M * 10^p, M its decimal
+ * significand without leading zeros, p the net power of ten.
+ * Exact tier, on the device: M <= 2^53 and |p| <= 22.  double(M) and 10^|p|
+ * are exact, so double(M) / 10^|p|, double(M) * 10^p or double(M) is one
+ * correctly rounded IEEE operation on exact operands (Clinger); the sign is
+ * applied last ("-0.0000" is -0.0).
+ * Three outcomes for a token: exact tier; UNDECIDED (inside the grammar,
+ * outside the tier: appended to undecided_dev as int64 (token number, byte
+ * offset, length), at most undecided_cap entries, then converted on the host
+ * by strtod and patched into the table; *n_undecided is their number); or
+ * outside the grammar.  The latter, and the other SL_PLY_* conditions, reject
+ * the WHOLE file: *status > 0, the table's content is undefined, and the
+ * caller reads the file with the host reader (whose result and exceptions are
+ * then the file's).  *status == SL_PLY_ACCEPTED: the table is complete.
+ * Returns SL_OK for either; SL_E* for bad arguments or a HIP failure.  Scratch
+ * (8 B per token) is the context's.  Blocking on `stream` (hipStream_t). */
+int sl_parse_ply_ascii(sl_ctx* ctx, const uint8_t* body_dev, int64_t n_bytes, int64_t n_rows, int n_cols,
+                       double* table_dev, int64_t* undecided_dev, int64_t undecided_cap, int64_t* n_undecided,
+                       int* status, void* stream);
+
+/* The binary_little_endian body: n_rows records of `stride` bytes at body_dev
+ * (device memory, no alignment asked: fields are read bytewise); property j is
+ * col_type[j] (SL_PLY_*) at byte col_offset[j] of the record (host arrays of
+ * n_cols) and is widened to f64 into table_dev, f64 [n_rows][n_cols].  Every
+ * property must lie inside the record (SL_EINVAL).  Blocking on `stream`. */
+int sl_unpack_ply_binary(sl_ctx* ctx, const uint8_t* body_dev, int64_t n_rows, int64_t stride, int n_cols,
+                         const int* col_offset, const int* col_type, double* table_dev, void* stream);
+
 /* ---- merge stage (server/processing.py:116-182) ----
  * Open3D's PointCloud::VoxelDownSample and RemoveStatisticalOutliers on a
  * device cloud (xyz f64 [n][3], bgr u8 [n][3] or NULL).  Blocking on `stream`;

@@ -29,6 +29,17 @@ SL_XYZ_F32 = 0
 SL_XYZ_F64 = 1
 SL_XYZ_F32_FAST = 2
 
+# *status of sl_parse_ply_ascii (ply.read_cloud_device's info["status"])
+SL_PLY_ACCEPTED = 0
+SL_PLY_BAD_BYTE = 1
+SL_PLY_BAD_TOKEN = 2
+SL_PLY_TOKEN_COUNT = 3
+SL_PLY_RAGGED_LINE = 4
+SL_PLY_COLOUR_RANGE = 5
+SL_PLY_UNDECIDED_OVERFLOW = 6
+# col_type of sl_unpack_ply_binary, by numpy dtype string (ply._PLY_TYPES)
+SL_PLY_TYPE = {"<f4": 0, "<f8": 1, "u1": 2, "i1": 3, "<i2": 4, "<u2": 5, "<i4": 6, "<u4": 7}
+
 # every symbol include/slgpu.h declares
 EXPORTS = ("sl_abi_version", "sl_ctx_create", "sl_ctx_destroy", "sl_ctx_last_error", "sl_ctx_reserve",
            "sl_set_calib", "sl_decode_triangulate", "sl_mask_counts_to", "sl_stack_ready", "sl_stack_next", "sl_call_prepare", "sl_call_run", "sl_call_destroy", "sl_triangulate_maps", "sl_sync",
@@ -43,6 +54,7 @@ EXPORTS = ("sl_abi_version", "sl_ctx_create", "sl_ctx_destroy", "sl_ctx_last_err
            "sl_information_matrix", "sl_pose_graph_optimize",
            "sl_radius_count", "sl_cluster_dbscan", "sl_cluster_dbscan_stats", "sl_nearest_neighbor_distance",
            "sl_ball_pivot_max_neighbours", "sl_ball_pivot_candidates", "sl_ball_pivot_candidates_stats",
+           "sl_parse_ply_ascii", "sl_unpack_ply_binary",
            "sl_decode_triangulate_batch", "sl_last_error")
 
 _vp = ctypes.c_void_p
@@ -128,6 +140,10 @@ _SIGS = {
     "sl_ball_pivot_candidates": (_i32, [_vp, _vp, _vp, _i64, ctypes.c_double, _vp, _vp, _i64, ctypes.POINTER(_i64),
                                          _vp]),
     "sl_ball_pivot_candidates_stats": (_i32, [ctypes.POINTER(ctypes.c_double), _i32]),
+    "sl_parse_ply_ascii": (_i32, [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _i64, ctypes.POINTER(_i64),
+                                  ctypes.POINTER(_i32), _vp]),
+    "sl_unpack_ply_binary": (_i32, [_vp, _vp, _i64, _i64, _i32, ctypes.POINTER(_i32), ctypes.POINTER(_i32), _vp,
+                                    _vp]),
     "sl_gather_unique_id": (_i32, [_vp]),
     "sl_gather_init": (_i32, [_vp, _i32, _i32, _vp]),
     "sl_gather_counts": (_i32, [_vp, _i64, _vp, _vp]),

@@ -2250,6 +2250,17 @@ struct sl_ctx {
   int64_t cap_ply_text = 0;
   char* h_ply_text = nullptr;
   int64_t cap_h_ply_text = 0;
+  // sl_parse_ply_ascii / sl_unpack_ply_binary (slplyread.inl): status words and
+  // the undecided counter, every token's byte offset, the patched values,
+  // the binary layout (d_ply_bsum / d_ply_boff hold the chunk counts and scan)
+  unsigned* d_plyr_state = nullptr;
+  int64_t cap_plyr_state = 0;
+  int64_t* d_plyr_tok = nullptr;
+  int64_t cap_plyr_tok = 0;
+  double* d_plyr_val = nullptr;
+  int64_t cap_plyr_val = 0;
+  int* d_plyr_cols = nullptr;
+  int64_t cap_plyr_cols = 0;
   int64_t cap_gcounts = 0;
   // the last call's stream: a call on another stream first waits for the work
   // queued there (the scratch above is per context)
@@ -3214,7 +3225,9 @@ void sl_ctx_destroy(sl_ctx* c) {
   }
   if (c->d_gcounts) (void)hipFree(c->d_gcounts);
   for (void* ptr : {static_cast<void*>(c->d_ply_bsum), static_cast<void*>(c->d_ply_boff),
-                    static_cast<void*>(c->d_ply_text)})
+                    static_cast<void*>(c->d_ply_text), static_cast<void*>(c->d_plyr_state),
+                    static_cast<void*>(c->d_plyr_tok), static_cast<void*>(c->d_plyr_val),
+                    static_cast<void*>(c->d_plyr_cols)})
     if (ptr) (void)hipFree(ptr);
   if (c->h_ply_text) (void)hipHostFree(c->h_ply_text);
   if (c->done_ev) (void)hipEventDestroy(c->done_ev);
@@ -4002,6 +4015,9 @@ int sl_write_ply_binary(const char* path, const void* xyz, int xyz_dtype, const 
 }
 
 }  // extern "C"
+
+// the reader of those files' bodies (uses k_ply_scan / ply_block_scan above)
+#include "slplyread.inl"
 
 
 extern "C" {

@@ -65,6 +65,14 @@ def _engine(device) -> core.Reconstructor:
         return _engines[idx]
 
 
+def _read_cloud(path, dev):
+    """ply.read_ply of a view's file, parsed on the device (ply.read_cloud_device) -> (points f64 [N,3],
+    colours BGR u8 [N,3], zeros when the file has none)."""
+    cloud = ply.read_cloud_device(path, device=dev)
+    P, C = cloud["points"], cloud["colors"]
+    return P, (C if C is not None else torch.zeros((len(P), 3), dtype=torch.uint8, device=dev))
+
+
 def _call(eng, name, *args):
     """One libslgpu entry point of the (ctx, ..., stream) shape, under the engine's lock, checked."""
     with eng._lock:
@@ -468,9 +476,7 @@ def merge_pro_360(input_folder, output_path, voxel_size: float = 0.02, *, seed_p
     eng = _engine(device)
     pcds = []
     for f in files:
-        P, C = ply.read_ply(f)
-        pcds.append((torch.from_numpy(np.ascontiguousarray(P, dtype=np.float64)).to(eng.device),
-                     torch.from_numpy(np.ascontiguousarray(C)).to(eng.device)))
+        pcds.append(_read_cloud(f, eng.device))
     print(f"[Merge 360] Loaded {len(pcds)} clouds. Running Sequential Registration (New360 Logic)...")
     down = {}
 
@@ -569,9 +575,9 @@ def merge_pro_360_posed(input_folder, output_path, poses, voxel_size: float = 0.
     eng = _engine(device)
     parts_p, parts_c = [], []
     for f, M in zip(files, poses):
-        P, C = ply.read_ply(f)
+        P, C = _read_cloud(f, eng.device)
         parts_p.append(transform(P, M, device=eng.device))
-        parts_c.append(torch.from_numpy(C).to(eng.device))
+        parts_c.append(C)
     print(f"[Merge 360] Loaded {len(files)} clouds. Applying the given poses...")
     return _finish_merge(parts_p, parts_c, voxel_size, output_path, binary, eng.device)
 
@@ -728,9 +734,7 @@ def merge_360_pose_graph(input_folder, output_path, voxel_size: float = 1.0, *, 
     eng = _engine(device)
     pcds = []
     for f in files:
-        P, C = ply.read_ply(f)
-        pcds.append((torch.from_numpy(np.ascontiguousarray(P, dtype=np.float64)).to(eng.device),
-                     torch.from_numpy(np.ascontiguousarray(C)).to(eng.device)))
+        pcds.append(_read_cloud(f, eng.device))
     graph = full_registration([p for p, _ in pcds], voxel_size, seed_poses=seed_poses, ransac_seed=ransac_seed,
                               device=eng.device)
     print("\nRunning Pose Graph Optimization...")

@@ -42,7 +42,7 @@ errors, and runs them on the GPU through ``merge`` (libslgpu.so):
 Without Open3D, "a point cloud object" is a ``Cloud(points, colors)`` of
 device tensors (f64 [N, 3], BGR u8 [N, 3] or None).  It is accepted wherever
 the reference accepts a path or an object and returned when ``return_obj`` is
-set.  Files are read with ``ply.read_ply`` and written with
+set.  Files are read with ``ply.read_cloud_device`` and written with
 ``ply.save_ply_open3d`` (the layout o3d.io.write_point_cloud writes).  A file
 that cannot be parsed loads as an empty cloud, as o3d.io.read_point_cloud
 returns one.
@@ -60,7 +60,6 @@ import argparse
 import glob
 import os
 
-import numpy as np
 import torch
 
 from . import merge, mesh, ply
@@ -85,19 +84,27 @@ def _write(path, cloud: Cloud) -> None:
     ply.save_ply_open3d(cloud.points.cpu().numpy(), C.cpu().numpy(), path)
 
 
+def _read_points_colors(path, dev):
+    """ply.read_ply of the file on the device (ply.read_cloud_device): points f64, colours BGR u8 (zeros when
+    the file has none)."""
+    cloud = ply.read_cloud_device(path, device=dev)
+    P, C = cloud["points"], cloud["colors"]
+    return P, (C if C is not None else torch.zeros((len(P), 3), dtype=torch.uint8, device=dev))
+
+
 class ProcessingLogic:
     @staticmethod
     def _load_pcd(input_data):
         if isinstance(input_data, str):
             if not os.path.exists(input_data):
                 raise FileNotFoundError(f"Input file not found: {input_data}")
-            try:
-                P, C = ply.read_ply(input_data)
-            except (ValueError, KeyError, IndexError):  # read_point_cloud: a warning and an empty cloud
-                P, C = np.zeros((0, 3)), np.zeros((0, 3), np.uint8)
             dev = merge._engine(None).device
-            return Cloud(torch.from_numpy(np.ascontiguousarray(P, dtype=np.float64)).to(dev),
-                         torch.from_numpy(np.ascontiguousarray(C)).to(dev))
+            try:
+                P, C = _read_points_colors(input_data, dev)
+            except (ValueError, KeyError, IndexError):  # read_point_cloud: a warning and an empty cloud
+                P = torch.zeros((0, 3), dtype=torch.float64, device=dev)
+                C = torch.zeros((0, 3), dtype=torch.uint8, device=dev)
+            return Cloud(P, C)
         return input_data
 
     @staticmethod
@@ -158,16 +165,15 @@ class ProcessingLogic:
     @staticmethod
     def _load_for_meshing(input_path):
         """-> (points, normals | None) on the device (a file that cannot be parsed: an empty cloud)."""
+        dev = merge._engine(None).device
         try:
-            P, _ = ply.read_ply(input_path)
-            N = ply.read_normals(input_path)
+            cloud = ply.read_cloud_device(input_path, device=dev)  # the file read and parsed once
+            P, N = cloud["points"], cloud["normals"]
         except (ValueError, KeyError, IndexError):
-            P, N = np.zeros((0, 3)), None
+            P, N = torch.zeros((0, 3), dtype=torch.float64, device=dev), None
         if len(P) == 0:
             raise ValueError("Point cloud is empty.")
-        dev = merge._engine(None).device
-        to = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)  # noqa: E731
-        return to(P), (None if N is None else to(N))
+        return P, N
 
     @staticmethod
     def reconstruct_stl(input_path, output_path, mode="watertight", params=None, *, budget_bytes=None,

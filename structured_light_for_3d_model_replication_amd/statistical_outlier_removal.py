@@ -20,7 +20,7 @@ Open3D's algorithms restated, parity with Open3D unpinned (not in this image),
 tests/cluster_oracle.py the CPU restatement.
 
 Without Open3D a point cloud is a ``processing.Cloud`` of device tensors; files
-are read with ``ply.read_ply`` and written with ``ply.save_ply_open3d`` (the
+are read with ``ply.read_cloud_device`` and written with ``ply.save_ply_open3d`` (the
 layout o3d.io.write_point_cloud writes), colours kept.  Left out: the
 ``draw_geometries`` preview that ends both recipes (a GUI window) with its
 "Visualizing..." line, and ``cluster_dbscan``'s progress bar.  A file without
@@ -32,7 +32,6 @@ from __future__ import annotations
 import argparse
 
 import numpy as np
-import torch
 
 from . import merge, ply
 from .processing import Cloud, _write
@@ -40,11 +39,8 @@ from .processing import Cloud, _write
 
 def _read(file_path) -> Cloud:
     """o3d.io.read_point_cloud: a ``Cloud`` on the device, ``colors`` None when the file has none."""
-    P, C = ply.read_ply(file_path)
-    has_colors = all(c in ply._read_columns(file_path) for c in ("red", "green", "blue"))
-    dev = merge._engine(None).device
-    return Cloud(torch.from_numpy(np.ascontiguousarray(P, dtype=np.float64)).to(dev),
-                 torch.from_numpy(np.ascontiguousarray(C)).to(dev) if has_colors else None)
+    cloud = ply.read_cloud_device(file_path, device=merge._engine(None).device)  # one read: colours or None
+    return Cloud(cloud["points"], cloud["colors"])
 
 
 def keep_largest_cluster(pcd: Cloud, eps=5, min_points=200) -> Cloud:
