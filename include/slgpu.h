@@ -588,6 +588,51 @@ int sl_mesh_remove_vertices(sl_ctx* ctx, const double* vertices, int64_t n_verti
                             int64_t n_triangles, const uint8_t* mask, double* out_vertices, int32_t* out_triangles,
                             int64_t* out_n_vertices, int64_t* out_n_triangles, void* stream);
 
+/* ---- mesh clean-up (csrc/slmeshclean.inl, which states the definitions) ----
+ * Open3D's cluster_connected_triangles / remove_triangles_by_mask /
+ * remove_unreferenced_vertices / simplify_vertex_clustering(Average), restated
+ * in order-free forms; tests/meshclean_oracle.py is their CPU form and the
+ * results equal it exactly.  vertices f64 [n_vertices][3], triangles int32
+ * [n_triangles][3] (device); n_vertices < 2^31, 3 n_triangles < 2^32.  A pass of
+ * its own reads every index first: one outside 0 .. n_vertices - 1 is SL_EINDEX
+ * and nothing is indexed.  Outputs are sized by the caller to the input's size;
+ * the true counts -> host.  Zero triangles / vertices succeed.  Blocking on
+ * `stream`.
+ *   sl_mesh_cluster_triangles    two triangles are adjacent iff they share an
+ *       edge (the unordered pair); a cluster is a connected component; its label
+ *       is the rank of its smallest triangle index among the clusters' smallest
+ *       indices.  -> triangle_clusters int32 [n_triangles], cluster_n_triangles
+ *       int64 [capacity n_triangles], the count -> *n_clusters; cluster_area f64
+ *       [capacity n_triangles] may be NULL (then `vertices` may be NULL too and
+ *       the sort by label is not run): the triangle areas in ascending index in
+ *       blocks of 64 from the cluster's first member, left folds from 0.0.
+ *       Lock-free union-find on the device; nothing spins.
+ *   sl_mesh_cluster_triangles_stats    the calling thread's last call's host
+ *       milliseconds per stage (edge keys, sort, union, flatten + rank, counts,
+ *       areas; stage_ms[capacity], zero-filled) -- a measurement aid.
+ *   sl_mesh_remove_triangles     mask u8 [n_triangles] (non-zero: remove); the
+ *       rest keep their order.  No index is read as an index.
+ *   sl_mesh_remove_unreferenced  the vertices of no triangle go, the rest keep
+ *       their order; out_triangles [n_triangles] re-indexed.
+ *   sl_mesh_simplify_clustering  sl_voxel_downsample's grid over all vertices
+ *       (its limits and messages; a non-finite vertex is SL_EINVAL); a voxel's
+ *       new index is the rank of its smallest member vertex, its vertex the mean
+ *       of its members summed in ascending index; triangles mapped, dropped when
+ *       two indices are equal, rotated so that the smallest index comes first,
+ *       the first occurrence of every triple kept, in input order. */
+int sl_mesh_cluster_triangles(sl_ctx* ctx, const double* vertices, int64_t n_vertices, const int32_t* triangles,
+                              int64_t n_triangles, int32_t* triangle_clusters, int64_t* cluster_n_triangles,
+                              double* cluster_area, int64_t* n_clusters, void* stream);
+int sl_mesh_cluster_triangles_stats(double* stage_ms, int capacity);
+int sl_mesh_remove_triangles(sl_ctx* ctx, const int32_t* triangles, int64_t n_triangles, const uint8_t* mask,
+                             int32_t* out_triangles, int64_t* out_n_triangles, void* stream);
+int sl_mesh_remove_unreferenced(sl_ctx* ctx, const double* vertices, int64_t n_vertices, const int32_t* triangles,
+                                int64_t n_triangles, double* out_vertices, int32_t* out_triangles,
+                                int64_t* out_n_vertices, void* stream);
+int sl_mesh_simplify_clustering(sl_ctx* ctx, const double* vertices, int64_t n_vertices, const int32_t* triangles,
+                                int64_t n_triangles, double voxel_size, double* out_vertices, int32_t* out_triangles,
+                                int64_t* out_n_vertices, int64_t* out_n_triangles, void* stream);
+
 /* ---- consistent tangent-plane normal orientation (processing.py:201, :282) ----
  * orient_normals_consistent_tangent_plane restated on the kNN graph alone
  * (csrc/slorient.inl; tests/orient_oracle.py is the CPU restatement, bit for

@@ -51,6 +51,8 @@ EXPORTS = ("sl_abi_version", "sl_ctx_create", "sl_ctx_destroy", "sl_ctx_last_err
            "sl_mesh_splat", "sl_mesh_unfix", "sl_mesh_divergence", "sl_mesh_sample", "sl_ordered_sum",
            "sl_orient_normals", "sl_mesh_extract_count", "sl_mesh_extract_emit", "sl_mesh_remove_vertices",
            "sl_orient_normals_mst", "sl_orient_normals_mst_stats",
+           "sl_mesh_cluster_triangles", "sl_mesh_cluster_triangles_stats", "sl_mesh_remove_triangles",
+           "sl_mesh_remove_unreferenced", "sl_mesh_simplify_clustering",
            "sl_information_matrix", "sl_pose_graph_optimize",
            "sl_radius_count", "sl_cluster_dbscan", "sl_cluster_dbscan_stats", "sl_nearest_neighbor_distance",
            "sl_ball_pivot_max_neighbours", "sl_ball_pivot_candidates", "sl_ball_pivot_candidates_stats",
@@ -124,6 +126,12 @@ _SIGS = {
                                     ctypes.c_double, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
     "sl_mesh_remove_vertices": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, ctypes.POINTER(_i64),
                                        ctypes.POINTER(_i64), _vp]),
+    "sl_mesh_cluster_triangles": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, ctypes.POINTER(_i64), _vp]),
+    "sl_mesh_cluster_triangles_stats": (_i32, [ctypes.POINTER(ctypes.c_double), _i32]),
+    "sl_mesh_remove_triangles": (_i32, [_vp, _vp, _i64, _vp, _vp, ctypes.POINTER(_i64), _vp]),
+    "sl_mesh_remove_unreferenced": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, ctypes.POINTER(_i64), _vp]),
+    "sl_mesh_simplify_clustering": (_i32, [_vp, _vp, _i64, _vp, _i64, ctypes.c_double, _vp, _vp,
+                                           ctypes.POINTER(_i64), ctypes.POINTER(_i64), _vp]),
     "sl_orient_normals_mst": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, ctypes.POINTER(_i64),
                                      ctypes.POINTER(_i64), _vp]),
     "sl_orient_normals_mst_stats": (_i32, [ctypes.POINTER(_i32), ctypes.POINTER(_i32), _i32]),

@@ -2183,3 +2183,5 @@ int sl_merge_pool_trim(int device, int64_t* released_bytes) {
 #include "slcluster.inl"
 // ball-pivoting surface meshing: the per-point enumeration of the triangles with an empty ball
 #include "slbpa.inl"
+// mesh clean-up: connected components of triangles, mask removal, vertex clustering
+#include "slmeshclean.inl"

@@ -27,6 +27,14 @@ pass bookkeeping -- vertex classes, edge counts, the seed and per-edge rules --
 is torch sorts and searches on the device.  tests/bpa_oracle.py is the CPU
 restatement the result equals exactly; the triangle set is not Open3D's.
 
+``cluster_connected_triangles``, ``remove_triangles_by_mask``,
+``remove_unreferenced_vertices``, ``select_components`` and
+``simplify_vertex_clustering`` clean the mesh before it is written: Open3D's
+calls of those names in order-free forms (csrc/slmeshclean.inl states them;
+tests/meshclean_oracle.py is their CPU form, which the results equal exactly).
+The drop-ins apply them when asked to (``keep_largest_component``,
+``min_component_triangles``, ``simplify_voxel_size``).
+
 Open3D's Poisson is the adaptive-octree variant and is not installed here:
 parity with Open3D is unpinned, and tests/mesh_oracle.py is the CPU restatement
 the tests check against -- bit for bit for every stage except the solve.
@@ -311,6 +319,138 @@ def remove_vertices_by_mask(vertices, triangles, mask, *, device=None):
     nv, nt = ctypes.c_int64(), ctypes.c_int64()
     _call(eng, "sl_mesh_remove_vertices", _ptr(Vx), len(Vx), _ptr(T), len(T), _ptr(M), _ptr(ov), _ptr(ot),
           ctypes.byref(nv), ctypes.byref(nt))
+    return ov[: nv.value], ot[: nt.value]
+
+
+def _tris(triangles, dev) -> torch.Tensor:
+    T = torch.as_tensor(triangles)
+    if T.numel() and (T.dim() != 2 or T.shape[1] != 3):
+        raise ValueError("triangles must be (T, 3)")
+    return T.to(device=dev, dtype=torch.int32).contiguous().reshape(-1, 3)
+
+
+def cluster_connected_triangles(vertices, triangles, *, n_vertices=None, area=True, device=None):
+    """TriangleMesh.cluster_connected_triangles -> (triangle_clusters int32 [T],
+    cluster_n_triangles int64 [C], cluster_area f64 [C] | None) on the device.
+    Two triangles are adjacent iff they share an edge (a shared vertex alone
+    does not connect); a cluster is a connected component and its label the
+    rank of its smallest triangle index, which is what Open3D's breadth-first
+    loop assigns (csrc/slmeshclean.inl states the rules, tests/meshclean_oracle.py
+    is their CPU form, which the result equals exactly).  The areas need the
+    vertices; labels and counts do not: ``vertices`` may be None when
+    ``n_vertices`` is given, and then (or with ``area=False``) no area is
+    computed and the sort by label it needs is not run.  Deviation: a cluster's
+    area is summed in ascending triangle index in blocks of 64 (Open3D: in
+    breadth-first order), so the last bits can differ.  An index outside
+    0 .. V - 1 raises IndexError."""
+    eng = _engine(device)
+    Vx = None if vertices is None else _f64(vertices, eng.device)
+    if Vx is None and n_vertices is None:
+        raise ValueError("vertices or n_vertices is needed")
+    nv = len(Vx) if n_vertices is None else int(n_vertices)
+    if Vx is not None and nv != len(Vx):
+        raise ValueError("n_vertices does not match the vertices")
+    T = _tris(triangles, eng.device)
+    t = len(T)
+    want = bool(area) and Vx is not None
+    labels = torch.empty(max(t, 1), dtype=torch.int32, device=eng.device)
+    counts = torch.empty(max(t, 1), dtype=torch.int64, device=eng.device)
+    areas = torch.empty(max(t, 1), dtype=torch.float64, device=eng.device) if want else None
+    nc = ctypes.c_int64()
+    _call(eng, "sl_mesh_cluster_triangles", _ptr(Vx) if Vx is not None and len(Vx) else None, nv,
+          _ptr(T) if t else None, t, _ptr(labels), _ptr(counts), _ptr(areas), ctypes.byref(nc))
+    return labels[:t], counts[: nc.value], (areas[: nc.value] if want else None)
+
+
+def cluster_stats(*, device=None) -> dict:
+    """Host milliseconds per stage of this thread's last ``cluster_connected_triangles``
+    (sl_mesh_cluster_triangles_stats; a measurement aid)."""
+    eng = _engine(device)
+    v = (ctypes.c_double * 6)()
+    _lib.check(eng._L.sl_mesh_cluster_triangles_stats(v, 6), None, "sl_mesh_cluster_triangles_stats")
+    return {"edge_keys_ms": v[0], "sort_ms": v[1], "union_ms": v[2], "flatten_rank_ms": v[3], "counts_ms": v[4],
+            "areas_ms": v[5]}
+
+
+def remove_triangles_by_mask(vertices, triangles, mask, *, device=None):
+    """TriangleMesh.remove_triangles_by_mask -> (vertices, triangles): the
+    masked triangles go and the rest keep their order; the vertices are
+    untouched, as in Open3D."""
+    eng = _engine(device)
+    Vx = _f64(vertices, eng.device)
+    T = _tris(triangles, eng.device)
+    M = torch.as_tensor(mask).to(device=eng.device).reshape(-1).ne(0).to(torch.uint8).contiguous()
+    if len(M) != len(T):
+        raise ValueError("a mask entry per triangle is needed")
+    out = torch.empty((max(len(T), 1), 3), dtype=torch.int32, device=eng.device)
+    nt = ctypes.c_int64()
+    _call(eng, "sl_mesh_remove_triangles", _ptr(T) if len(T) else None, len(T), _ptr(M), _ptr(out), ctypes.byref(nt))
+    return Vx, out[: nt.value]
+
+
+def remove_unreferenced_vertices(vertices, triangles, *, device=None):
+    """TriangleMesh.remove_unreferenced_vertices -> (vertices, triangles): the
+    vertices of no triangle go, the rest keep their order, and the triangles
+    are re-indexed.  An index outside 0 .. V - 1 raises IndexError."""
+    eng = _engine(device)
+    Vx = _f64(vertices, eng.device)
+    T = _tris(triangles, eng.device)
+    ov = torch.empty((max(len(Vx), 1), 3), dtype=torch.float64, device=eng.device)
+    ot = torch.empty((max(len(T), 1), 3), dtype=torch.int32, device=eng.device)
+    nv = ctypes.c_int64()
+    _call(eng, "sl_mesh_remove_unreferenced", _ptr(Vx) if len(Vx) else None, len(Vx), _ptr(T) if len(T) else None,
+          len(T), _ptr(ov), _ptr(ot), ctypes.byref(nv))
+    return ov[: nv.value], ot[: len(T)]
+
+
+def select_components(vertices, triangles, *, keep_largest: bool = False, min_triangles=None, device=None):
+    """cluster_connected_triangles + remove_triangles_by_mask +
+    remove_unreferenced_vertices -> (vertices, triangles): ``min_triangles``
+    first drops the clusters with fewer triangles, then ``keep_largest`` keeps
+    the remaining cluster with the most triangles (the lowest label on a tie),
+    then the unreferenced vertices are removed."""
+    eng = _engine(device)
+    Vx = _f64(vertices, eng.device)
+    T = _tris(triangles, eng.device)
+    labels, counts, _ = cluster_connected_triangles(Vx, T, area=False, device=eng.device)
+    keep = torch.ones(len(counts), dtype=torch.bool, device=eng.device)
+    if min_triangles is not None:
+        keep &= counts >= int(min_triangles)
+    if keep_largest and bool(keep.any()):
+        c = torch.where(keep, counts, torch.full_like(counts, -1))
+        first = torch.nonzero(c == c.max())[0, 0]  # the lowest label on a tie
+        keep = torch.zeros_like(keep)
+        keep[first] = True
+    mask = ~keep[labels.to(torch.int64)]
+    _, T = remove_triangles_by_mask(Vx, T, mask, device=eng.device)
+    return remove_unreferenced_vertices(Vx, T, device=eng.device)
+
+
+def simplify_vertex_clustering(vertices, triangles, voxel_size: float, *, device=None):
+    """TriangleMesh.simplify_vertex_clustering(voxel_size, contraction=Average)
+    -> (vertices f64 [V', 3], triangles int32 [T', 3]) on the device.  The grid
+    is ``merge.voxel_down_sample``'s over all vertices, referenced or not
+    (lo = min - voxel_size / 2; its limits and messages).  A voxel's new index
+    is the rank of its smallest member vertex index (Open3D's first-encounter
+    numbering) and its vertex the members' mean, summed in ascending vertex
+    index.  Triangles, in input order: mapped, dropped when two indices are
+    equal, rotated so that the smallest index comes first (the orientation is
+    kept; the opposite orientation is another triple), the first occurrence of
+    every triple kept.  Deviations: Open3D sums a voxel's members and emits the
+    triangles in the order of an unordered_set; here both orders are fixed (the
+    last bits of a vertex can differ, and the triangles come in input order of
+    their first occurrences).  The result is in general NOT manifold -- edges
+    with more than two triangles and holes appear where the surface is thinner
+    than a voxel; that is the algorithm, and nothing repairs it.  A non-finite
+    vertex raises ValueError, an index outside 0 .. V - 1 IndexError."""
+    eng = _engine(device)
+    Vx = _f64(vertices, eng.device)
+    T = _tris(triangles, eng.device)
+    ov = torch.empty((max(len(Vx), 1), 3), dtype=torch.float64, device=eng.device)
+    ot = torch.empty((max(len(T), 1), 3), dtype=torch.int32, device=eng.device)
+    nv, nt = ctypes.c_int64(), ctypes.c_int64()
+    _call(eng, "sl_mesh_simplify_clustering", _ptr(Vx) if len(Vx) else None, len(Vx), _ptr(T) if len(T) else None,
+          len(T), float(voxel_size), _ptr(ov), _ptr(ot), ctypes.byref(nv), ctypes.byref(nt))
     return ov[: nv.value], ot[: nt.value]
 
 

@@ -36,7 +36,14 @@ errors, and runs them on the GPU through ``merge`` (libslgpu.so):
   ``mesh.create_from_point_cloud_ball_pivoting``, Open3D's sequential front
   restated in an order-free form (csrc/slbpa.inl; the triangle set is not
   Open3D's, which depends on its visiting order).  It stays opt-in until it has
-  run on real scans.  Only ``.stl`` can be written; a depth whose grids do not
+  run on real scans.  Three more keyword-only arguments of both methods clean
+  the mesh after the density trim (and after ball pivoting) and before it is
+  written, each with a line of the counts before and after:
+  ``keep_largest_component`` and ``min_component_triangles``
+  (``mesh.select_components``: the islands the trim cuts off and the bubbles
+  Poisson closes around stray blobs) and then ``simplify_voxel_size``
+  (``mesh.simplify_vertex_clustering``; csrc/slmeshclean.inl).  With all three
+  at their defaults nothing changes.  Only ``.stl`` can be written; a depth whose grids do not
   fit the device raises MemoryError (depth 10 is the largest).
 
 Without Open3D, "a point cloud object" is a ``Cloud(points, colors)`` of
@@ -176,8 +183,24 @@ class ProcessingLogic:
         return P, N
 
     @staticmethod
+    def _clean_mesh(tag, V, T, keep_largest_component, min_component_triangles, simplify_voxel_size):
+        """The opt-in clean-up of the drop-ins' mesh (mesh.select_components, then
+        mesh.simplify_vertex_clustering); a line with the counts before and after per applied step."""
+        if keep_largest_component or min_component_triangles is not None:
+            before = len(T)
+            V, T = mesh.select_components(V, T, keep_largest=bool(keep_largest_component),
+                                          min_triangles=min_component_triangles, device=V.device)
+            print(f"[{tag}] Selecting components: {before} -> {len(T)} triangles")
+        if simplify_voxel_size is not None:
+            before = len(T)
+            V, T = mesh.simplify_vertex_clustering(V, T, simplify_voxel_size, device=V.device)
+            print(f"[{tag}] Vertex clustering (voxel_size={simplify_voxel_size}): {before} -> {len(T)} triangles")
+        return V, T
+
+    @staticmethod
     def reconstruct_stl(input_path, output_path, mode="watertight", params=None, *, budget_bytes=None,
-                        tangent_planes=None, ball_pivoting=False):
+                        tangent_planes=None, ball_pivoting=False, keep_largest_component=False,
+                        min_component_triangles=None, simplify_voxel_size=None):
         if not os.path.exists(input_path):
             raise FileNotFoundError(f"Input file not found: {input_path}")
         params = {} if params is None else params
@@ -218,6 +241,8 @@ class ProcessingLogic:
                 raise ValueError(f"Invalid radii parameters: {e}")
         else:
             raise ValueError(f"Unknown mode: {mode}")
+        V, T = ProcessingLogic._clean_mesh("Recon", V, T, keep_largest_component, min_component_triangles,
+                                           simplify_voxel_size)
         if len(V) == 0:
             raise ValueError("Generated mesh is empty.")
         print("[Recon] Computing normals and saving...")
@@ -226,7 +251,8 @@ class ProcessingLogic:
 
     @staticmethod
     def mesh_360(input_path, output_path, depth=10, density_trim=0.01, orientation_mode="tangent", *,
-                 budget_bytes=None, tangent_planes=None):
+                 budget_bytes=None, tangent_planes=None, keep_largest_component=False, min_component_triangles=None,
+                 simplify_voxel_size=None):
         if not os.path.exists(input_path):
             raise FileNotFoundError(f"Input file not found: {input_path}")
         print(f"[360 Mesh] Loading {input_path}...")
@@ -263,6 +289,8 @@ class ProcessingLogic:
                 V, T = mesh.trim_by_density(V, T, densities, density_trim, device=P.device)
         else:
             print("[360 Mesh] Density trim is 0.0 -> Keeping watertight result.")
+        V, T = ProcessingLogic._clean_mesh("360 Mesh", V, T, keep_largest_component, min_component_triangles,
+                                           simplify_voxel_size)
         mesh.write_triangle_mesh(output_path, V, T)
         print(f"[360 Mesh] Saved to {output_path}")
 
