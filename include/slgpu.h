@@ -633,6 +633,43 @@ int sl_mesh_simplify_clustering(sl_ctx* ctx, const double* vertices, int64_t n_v
                                 int64_t n_triangles, double voxel_size, double* out_vertices, int32_t* out_triangles,
                                 int64_t* out_n_vertices, int64_t* out_n_triangles, void* stream);
 
+/* ---- mesh output (csrc/slmeshwrite.inl, which states the arithmetic) ----
+ * o3d.io.write_triangle_mesh for .stl and .ply after compute_vertex_normals(),
+ * from a mesh in device memory: vertices f64 [n_vertices][3], triangles int32
+ * [n_triangles][3], both counts < 2^31.  Every index is checked on the device
+ * first: one outside 0 .. n_vertices - 1 is SL_EINDEX, and a writer then
+ * neither creates nor touches `path`.  Blocking on `stream`.
+ *   sl_mesh_triangle_normals   out f64 [n_triangles][3]: (p1 - p0) x (p2 - p0)
+ *       over its length, zero for a zero length: the bits of
+ *       tests/mesh_oracle.py's triangle_normals.
+ *   sl_mesh_vertex_normals     out f64 [n_vertices][3]: per vertex the sum over
+ *       its triangles of llrint(unit normal 2^40) in wrapping 64-bit integers,
+ *       normalised; (0, 0, 1) for a zero sum.  Deviation: Open3D sums in f64 in
+ *       triangle order.  Exact against tests/meshwrite_oracle.py.
+ *   sl_write_stl_device        binary STL: 80 zero bytes, the count, 50-byte
+ *       records (float32 normal and corners, a zero attribute).
+ *   sl_write_mesh_ply_device   binary little-endian PLY in Open3D's layout:
+ *       double x y z nx ny nz per vertex, uchar 3 + three uint per face.
+ *     The records are packed on the device and come back through a ring of two
+ *     pinned chunks of `chunk_triangles` triangles (0: 655 360, i.e. 32 768 000
+ *     bytes; other values are rounded up to a multiple of 256; at most 8 times
+ *     the default), kept with the context: staging does not grow with the mesh.
+ *     The file is opened as sl_write_ply opens it.  SL_EIO: the file could not
+ *     be opened or written; SL_EHIP: a launch or copy failed (nothing more is
+ *     queued after it).  path NULL packs and copies without a file (measurement).
+ *   sl_mesh_write_stats        the calling thread's last writer call: host
+ *       milliseconds waiting for chunks, in write(), and in all (stage_ms
+ *       [capacity], zero-filled) -- a measurement aid. */
+int sl_mesh_triangle_normals(sl_ctx* ctx, const double* vertices, int64_t n_vertices, const int32_t* triangles,
+                             int64_t n_triangles, double* out, void* stream);
+int sl_mesh_vertex_normals(sl_ctx* ctx, const double* vertices, int64_t n_vertices, const int32_t* triangles,
+                           int64_t n_triangles, double* out, void* stream);
+int sl_write_stl_device(sl_ctx* ctx, const char* path, const double* vertices, int64_t n_vertices,
+                        const int32_t* triangles, int64_t n_triangles, int64_t chunk_triangles, void* stream);
+int sl_write_mesh_ply_device(sl_ctx* ctx, const char* path, const double* vertices, int64_t n_vertices,
+                             const int32_t* triangles, int64_t n_triangles, int64_t chunk_triangles, void* stream);
+int sl_mesh_write_stats(double* stage_ms, int capacity);
+
 /* ---- consistent tangent-plane normal orientation (processing.py:201, :282) ----
  * orient_normals_consistent_tangent_plane restated on the kNN graph alone
  * (csrc/slorient.inl; tests/orient_oracle.py is the CPU restatement, bit for

@@ -2262,6 +2262,10 @@ struct sl_ctx {
   int* d_plyr_cols = nullptr;
   int64_t cap_plyr_cols = 0;
   int64_t cap_gcounts = 0;
+  // sl_write_stl_device / sl_write_mesh_ply_device (slmeshwrite.inl): the ring of device and pinned chunk
+  // slots, owned by that file (slgpu_mesh_ring) and released with the context
+  void* mesh_ring = nullptr;
+  void (*mesh_ring_release)(void*) = nullptr;
   // the last call's stream: a call on another stream first waits for the work
   // queued there (the scratch above is per context)
   hipStream_t last_stream = nullptr;
@@ -3186,6 +3190,13 @@ void ply_format(const void* xyz, int xyz_dtype, const uint8_t* bgr, int64_t n, i
 
 }  // namespace
 
+// for slmerge.hip (slmeshwrite.inl): the mesh writers open their files as the PLY writers do
+int slgpu_open_replacing(const char* path) { return open_replacing(path); }
+void** slgpu_mesh_ring(sl_ctx* c, void (*release)(void*)) {
+  c->mesh_ring_release = release;
+  return &c->mesh_ring;
+}
+
 extern "C" {
 
 int sl_abi_version(void) { return SL_ABI_VERSION; }
@@ -3230,6 +3241,7 @@ void sl_ctx_destroy(sl_ctx* c) {
                     static_cast<void*>(c->d_plyr_cols)})
     if (ptr) (void)hipFree(ptr);
   if (c->h_ply_text) (void)hipHostFree(c->h_ply_text);
+  if (c->mesh_ring && c->mesh_ring_release) c->mesh_ring_release(c->mesh_ring);
   if (c->done_ev) (void)hipEventDestroy(c->done_ev);
   for (hipEvent_t e : c->prof_ev) (void)hipEventDestroy(e);
   for (void* ptr : {static_cast<void*>(c->d_planes), static_cast<void*>(c->d_xn), static_cast<void*>(c->d_yn),

@@ -2185,3 +2185,5 @@ int sl_merge_pool_trim(int device, int64_t* released_bytes) {
 #include "slbpa.inl"
 // mesh clean-up: connected components of triangles, mask removal, vertex clustering
 #include "slmeshclean.inl"
+// mesh output: triangle and vertex normals, STL and PLY records packed on the device and streamed to the file
+#include "slmeshwrite.inl"

@@ -1,0 +1,552 @@
+// libslgpu.so, part 2j -- writing a triangle mesh from device memory, included at
+// the end of slmerge.hip (one translation unit: it shares that file's scratch
+// pool and slmeshclean.inl's index check).  o3d.io.write_triangle_mesh for
+// ``.stl`` and ``.ply`` after compute_vertex_normals(): the records are packed
+// on the device and streamed to the file through a small ring of pinned chunks.
+// Open3D is not in this image, so its PLY layout and its NormalizeNormals rule
+// are restated from memory and UNPINNED; tests/mesh_oracle.py (STL, triangle
+// normals) and tests/meshwrite_oracle.py (vertex normals, PLY) are the CPU
+// forms the results equal byte for byte.
+//
+// Input: vertices f64 [V][3], triangles int32 [T][3]; V, T < 2^31.  Every index
+// is read by k_mc_check before the file is opened: one outside 0 .. V-1 is
+// SL_EINDEX, the path is not touched.
+//
+//   triangle normal   e1 = p1 - p0, e2 = p2 - p0, n = e1 x e2 (n0 = e1y e2z - e1z
+//              e2y, n1 = e1z e2x - e1x e2z, n2 = e1x e2y - e1y e2x), ln = sqrt((n0 n0
+//              + n1 n1) + n2 n2), n / ln, or +0 three times when ln == 0; f64,
+//              uncontracted, sqrt and division correctly rounded: the bits of the
+//              host writer and of mesh_oracle.triangle_normals.
+//   vertex normal     every triangle adds q_c = llrint(n_c 2^40) (ties to even; 0
+//              unless |n_c 2^40| < 2^62, so a NaN adds nothing) of its unit normal to
+//              the three sums of each of its three vertices: wrapping 64-bit
+//              integer atomics.  s_c = double(sum_c) (nearest even); a vertex with
+//              three zero sums (in no triangle, or normals that cancel) gets (0, 0,
+//              1), every other s / sqrt((sx sx + sy sy) + sz sz): the scale cancels
+//              and is not divided out.  DEVIATION: Open3D adds the f64 unit normals
+//              in triangle order, which is a traversal; fixed-point sums stand in
+//              for them, so the result does not depend on any order and repeats.
+//   STL record        50 bytes: float(n), float(p0), float(p1), float(p2) (f64 ->
+//              f32 to nearest even, overflow to +-inf, -0 kept), a zero uint16.
+//   PLY               "ply / format binary_little_endian 1.0 / comment Created by
+//              Open3D / element vertex V / property double x y z nx ny nz /
+//              element face T / property list uchar uint vertex_indices /
+//              end_header", V records of six doubles (48 bytes), T records of the
+//              byte 3 and three uint32 (13 bytes).
+//
+// Packing.  Neither 50 nor 13 is a multiple of 4: a thread per record storing to
+// global memory would scatter 1- and 2-byte stores.  A workgroup of 256 threads
+// builds the image of 256 records in LDS (12 800 B / 3 328 B, multiples of 16)
+// and, after one barrier, stores it lane-linear in 16-byte lines (1 KiB per wave
+// store) to the 16-byte-aligned slot.  The LDS writes are free of bank conflicts
+// (ds_write_b32: bank = dword mod 32 within a 32-lane half):
+//   STL   two records are 25 dwords.  The even record of pair p is dwords 25 p ..
+//         25 p + 11 and the low half of dword 25 p + 12, which is its zero
+//         attribute; the odd one starts in the high half of that dword and ends
+//         with its own zero attribute in the high half of dword 25 p + 24.  Both
+//         attributes being constants, the even record's thread writes 12 whole
+//         dwords and the odd one's 13, from its own floats alone.  Threads 0..127
+//         take the even records and 128..255 the odd ones, so a wave writes one
+//         dword per lane at a stride of 25 dwords: 32 consecutive p give 32
+//         different banks.
+//   PLY   four faces are 13 dwords; record r starts at byte r mod 4 of a dword.
+//         Wave k takes the records with r mod 4 == k (r = 4 lane + k), so the
+//         shape of a record's writes -- leading bytes up to the dword boundary,
+//         whole dwords, trailing bytes -- is wave-uniform and the stride is 13
+//         dwords: conflict-free again.  The partial dwords are written as 1- and
+//         2-byte LDS stores by the two records that share them.
+// The threads of a wave read every second (fourth) index triple; the waves of
+// the workgroup touch the same lines, which the vector cache serves.
+//
+// Streaming.  The body never exists as a whole: a ring of kRing slots, each a
+// device buffer and a pinned host buffer of one chunk (default 655 360
+// triangles, 32 768 000 B), allocated once per context and kept (they grow only
+// when a larger chunk is asked for, up to kMaxChunkTriangles).  On the caller's
+// stream chunk k is packed into device slot k mod kRing, copied to pinned slot k
+// mod kRing and followed by an event; the host writes chunk k after its event,
+// and chunk k + kRing is queued only after chunk k has been written.  Staging is
+// kRing (slot + slot) bytes whatever T is; the PLY writer also holds the 24 V
+// bytes of the vertex sums.  After a failed launch, copy or write nothing more is
+// queued, and what was queued is waited for before the call returns.
+
+#include <errno.h>
+#include <unistd.h>
+
+#include <chrono>
+#include <string>
+
+// from slgpu.hip: open_replacing, and the context's slot for the ring below (freed with the context by `release`)
+int slgpu_open_replacing(const char* path);
+void** slgpu_mesh_ring(sl_ctx* c, void (*release)(void*));
+
+namespace {
+namespace mwr {
+
+constexpr int kRing = 2;
+constexpr int64_t kChunkTriangles = 655360;                      // 32 768 000 B of STL records
+constexpr int64_t kMaxChunkTriangles = 8 * kChunkTriangles;
+constexpr int kStlRec = 50, kFaceRec = 13, kVertexRec = 48;
+constexpr int kStlLines = kT * kStlRec / 16, kFaceLines = kT * kFaceRec / 16;  // 800, 208
+constexpr double kVnFix = 1099511627776.0;                       // 2^40
+constexpr double kVnFixMax = 4611686018427387904.0;              // 2^62
+
+thread_local double tls_ms[3];  // waiting for chunks to land, writing them, the whole call
+
+// The corners of triangle t and its unit normal (the header's arithmetic).
+__device__ __forceinline__ void tri_normal(const double* __restrict__ verts, const int32_t* __restrict__ tris, int64_t t,
+                                           double* p, double* n) {
+  const int64_t a = tris[3 * t], b = tris[3 * t + 1], c = tris[3 * t + 2];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    p[k] = verts[3 * a + k];
+    p[3 + k] = verts[3 * b + k];
+    p[6 + k] = verts[3 * c + k];
+  }
+  const double e10 = p[3] - p[0], e11 = p[4] - p[1], e12 = p[5] - p[2];
+  const double e20 = p[6] - p[0], e21 = p[7] - p[1], e22 = p[8] - p[2];
+  const double n0 = e11 * e22 - e12 * e21, n1 = e12 * e20 - e10 * e22, n2 = e10 * e21 - e11 * e20;
+  const double ln = sqrt((n0 * n0 + n1 * n1) + n2 * n2);
+  const bool flat = ln == 0.0;
+  n[0] = flat ? 0.0 : n0 / ln;
+  n[1] = flat ? 0.0 : n1 / ln;
+  n[2] = flat ? 0.0 : n2 / ln;
+}
+
+__global__ __launch_bounds__(kT) void k_mw_tri_normals(const double* __restrict__ verts,
+                                                       const int32_t* __restrict__ tris, int64_t n_t,
+                                                       double* __restrict__ out) {
+  const int64_t t = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
+  if (t >= n_t) return;
+  double p[9], n[3];
+  tri_normal(verts, tris, t, p, n);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) out[3 * t + k] = n[k];
+}
+
+__device__ __forceinline__ int64_t vn_fix(double v) {
+  const double t = v * kVnFix;
+  return fabs(t) < kVnFixMax ? llrint(t) : 0;
+}
+
+// sums[v][c] += vn_fix(n_c) for the three vertices of every triangle (wrapping)
+__global__ __launch_bounds__(kT) void k_mw_vn_add(const double* __restrict__ verts, const int32_t* __restrict__ tris,
+                                                  int64_t n_t, unsigned long long* __restrict__ sums) {
+  const int64_t t = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
+  if (t >= n_t) return;
+  double p[9], n[3];
+  tri_normal(verts, tris, t, p, n);
+  unsigned long long q[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) q[k] = static_cast<unsigned long long>(vn_fix(n[k]));
+  if (!(q[0] | q[1] | q[2])) return;
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const int64_t v = tris[3 * t + j];
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+      if (q[k]) atomicAdd(sums + 3 * v + k, q[k]);
+  }
+}
+
+__device__ __forceinline__ void vn_of(const int64_t* __restrict__ sums, int64_t v, double* n) {
+  const double sx = static_cast<double>(sums[3 * v]), sy = static_cast<double>(sums[3 * v + 1]),
+               sz = static_cast<double>(sums[3 * v + 2]);
+  if (sx == 0.0 && sy == 0.0 && sz == 0.0) {
+    n[0] = n[1] = 0.0;
+    n[2] = 1.0;
+    return;
+  }
+  const double len = sqrt((sx * sx + sy * sy) + sz * sz);
+  n[0] = sx / len;
+  n[1] = sy / len;
+  n[2] = sz / len;
+}
+
+__global__ __launch_bounds__(kT) void k_mw_vn_norm(const int64_t* __restrict__ sums, int64_t n_v,
+                                                   double* __restrict__ out) {
+  const int64_t v = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
+  if (v >= n_v) return;
+  double n[3];
+  vn_of(sums, v, n);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) out[3 * v + k] = n[k];
+}
+
+// Store the first `bytes` bytes (rounded up to whole 16-byte lines) of the workgroup's LDS image.
+__device__ __forceinline__ void store_lines(const uint4* img, int bytes, uint4* __restrict__ out) {
+  const int lines = (bytes + 15) >> 4;
+  for (int i = threadIdx.x; i < lines; i += kT) out[i] = img[i];
+}
+
+// STL records of the triangles t0 .. t0 + count - 1 -> out (16-byte aligned, room for whole workgroups).
+__global__ __launch_bounds__(kT) void k_mw_pack_stl(const double* __restrict__ verts, const int32_t* __restrict__ tris,
+                                                    int64_t t0, int64_t count, uint4* __restrict__ out) {
+  __shared__ uint4 img4[kStlLines];
+  uint32_t* img = reinterpret_cast<uint32_t*>(img4);
+  const int t = threadIdx.x;
+  const int odd = t >> 7, pair = t & 127, r = 2 * pair + odd;
+  const int64_t first = static_cast<int64_t>(blockIdx.x) * kT;
+  uint32_t f[12];
+  if (first + r < count) {
+    double p[9], n[3];
+    tri_normal(verts, tris, t0 + first + r, p, n);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) f[k] = __float_as_uint(static_cast<float>(n[k]));
+#pragma unroll
+    for (int k = 0; k < 9; ++k) f[3 + k] = __float_as_uint(static_cast<float>(p[k]));
+  } else {
+#pragma unroll
+    for (int k = 0; k < 12; ++k) f[k] = 0u;
+  }
+  uint32_t* o = img + 25 * pair;
+  if (!odd) {  // (wave-uniform)
+#pragma unroll
+    for (int k = 0; k < 12; ++k) o[k] = f[k];
+  } else {
+    o[12] = f[0] << 16;  // the low half: the even record's attribute
+#pragma unroll
+    for (int k = 0; k < 11; ++k) o[13 + k] = (f[k] >> 16) | (f[k + 1] << 16);
+    o[24] = f[11] >> 16;  // the high half: this record's attribute
+  }
+  __syncthreads();
+  const int live = static_cast<int>(min<int64_t>(kT, count - first));
+  store_lines(img4, live * kStlRec, out + static_cast<int64_t>(blockIdx.x) * kStlLines);
+}
+
+// Bytes i .. i + 3 of the 13-byte face record (lo: bytes 0-7, hi: bytes 8-12), zero beyond it.
+__device__ __forceinline__ uint32_t face_bytes(uint64_t lo, uint64_t hi, int i) {
+  if (i == 0) return static_cast<uint32_t>(lo);
+  if (i < 8) return static_cast<uint32_t>((lo >> (8 * i)) | (hi << (64 - 8 * i)));
+  return static_cast<uint32_t>(hi >> (8 * (i - 8)));
+}
+
+// One record's 13 bytes at img + 13 r with r mod 4 == K: bytes up to the dword boundary, dwords, the rest.
+template <int K>
+__device__ __forceinline__ void put_face(unsigned char* o, uint64_t lo, uint64_t hi) {
+  constexpr int head = (4 - K) & 3;  // 0, 3, 2, 1
+  if (head & 1) o[0] = static_cast<unsigned char>(face_bytes(lo, hi, 0));
+  if (head & 2) *reinterpret_cast<uint16_t*>(o + (head & 1)) = static_cast<uint16_t>(face_bytes(lo, hi, head & 1));
+  constexpr int words = (kFaceRec - head) / 4, tail = (kFaceRec - head) % 4;  // 3/1, 2/2, 2/3, 3/0
+#pragma unroll
+  for (int w = 0; w < words; ++w) *reinterpret_cast<uint32_t*>(o + head + 4 * w) = face_bytes(lo, hi, head + 4 * w);
+  constexpr int at = head + 4 * words;
+  if (tail & 2) *reinterpret_cast<uint16_t*>(o + at) = static_cast<uint16_t>(face_bytes(lo, hi, at));
+  if (tail & 1) o[at + (tail & 2)] = static_cast<unsigned char>(face_bytes(lo, hi, at + (tail & 2)));
+}
+
+// PLY face records of the triangles t0 .. t0 + count - 1 -> out (as k_mw_pack_stl).
+__global__ __launch_bounds__(kT) void k_mw_pack_faces(const int32_t* __restrict__ tris, int64_t t0, int64_t count,
+                                                      uint4* __restrict__ out) {
+  __shared__ uint4 img4[kFaceLines];
+  unsigned char* img = reinterpret_cast<unsigned char*>(img4);
+  const int t = threadIdx.x;
+  const int k = t >> 6, r = 4 * (t & 63) + k;
+  const int64_t first = static_cast<int64_t>(blockIdx.x) * kT;
+  uint64_t lo = 0, hi = 0;
+  if (first + r < count) {
+    const int64_t g = t0 + first + r;
+    const uint64_t a = static_cast<uint32_t>(tris[3 * g]), b = static_cast<uint32_t>(tris[3 * g + 1]),
+                   c = static_cast<uint32_t>(tris[3 * g + 2]);
+    lo = 3u | (a << 8) | (b << 40);
+    hi = (b >> 24) | (c << 8);
+  }
+  unsigned char* o = img + kFaceRec * r;
+  switch (k) {  // (wave-uniform)
+    case 0: put_face<0>(o, lo, hi); break;
+    case 1: put_face<1>(o, lo, hi); break;
+    case 2: put_face<2>(o, lo, hi); break;
+    default: put_face<3>(o, lo, hi); break;
+  }
+  __syncthreads();
+  const int live = static_cast<int>(min<int64_t>(kT, count - first));
+  store_lines(img4, live * kFaceRec, out + static_cast<int64_t>(blockIdx.x) * kFaceLines);
+}
+
+// PLY vertex records of the vertices v0 .. v0 + count - 1: x y z nx ny nz, one double per thread.
+__global__ __launch_bounds__(kT) void k_mw_pack_vertices(const double* __restrict__ verts,
+                                                         const int64_t* __restrict__ sums, int64_t v0, int64_t count,
+                                                         double* __restrict__ out) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
+  if (i >= 6 * count) return;
+  const int64_t v = v0 + i / 6;
+  const int k = static_cast<int>(i % 6);
+  if (k < 3) {
+    out[i] = verts[3 * v + k];
+  } else {
+    double n[3];
+    vn_of(sums, v, n);
+    out[i] = n[k - 3];
+  }
+}
+
+// ---- host
+struct Ring {
+  char* dev[kRing] = {};
+  char* pin[kRing] = {};
+  hipEvent_t ev[kRing] = {};
+  int64_t cap = 0;  // bytes of every slot
+};
+
+void ring_drop_slots(Ring* r) {
+  for (int i = 0; i < kRing; ++i) {
+    if (r->dev[i]) (void)hipFree(r->dev[i]);
+    if (r->pin[i]) (void)hipHostFree(r->pin[i]);
+    r->dev[i] = r->pin[i] = nullptr;
+  }
+  r->cap = 0;
+}
+
+void ring_release(void* p) {
+  Ring* r = static_cast<Ring*>(p);
+  ring_drop_slots(r);
+  for (hipEvent_t e : r->ev)
+    if (e) (void)hipEventDestroy(e);
+  delete r;
+}
+
+// The context's ring with slots of at least `bytes` (idle between calls: a writer waits for all it queued).
+int ring_reserve(sl_ctx* c, int64_t bytes, Ring** out) {
+  void** slot = slgpu_mesh_ring(c, ring_release);
+  if (!*slot) *slot = new Ring();
+  Ring* r = static_cast<Ring*>(*slot);
+  for (hipEvent_t& e : r->ev)
+    if (!e) MTRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  if (r->cap < bytes) {
+    ring_drop_slots(r);
+    for (int i = 0; i < kRing; ++i) {
+      MTRY(c, hipMalloc(reinterpret_cast<void**>(&r->dev[i]), static_cast<size_t>(bytes)));
+      MTRY(c, hipHostMalloc(reinterpret_cast<void**>(&r->pin[i]), static_cast<size_t>(bytes), hipHostMallocDefault));
+    }
+    r->cap = bytes;
+  }
+  *out = r;
+  return SL_OK;
+}
+
+// The ring's order.  enqueue(k, slot): chunk k's work and the slot's event onto the stream; landed(slot): wait
+// for that event; sink(k, slot): consume the pinned slot.  Chunk k + ring is queued only after chunk k was
+// consumed; after a failure nothing more is queued, and everything queued is still waited for.
+template <class Enqueue, class Landed, class Sink>
+int stream_chunks(int64_t n_chunks, int ring, Enqueue enqueue, Landed landed, Sink sink) {
+  int64_t queued = 0;
+  bool dev_ok = true, io_ok = true;
+  for (int64_t k = 0; k < n_chunks; ++k) {
+    while (dev_ok && io_ok && queued < n_chunks && queued < k + ring) {
+      dev_ok = enqueue(queued, static_cast<int>(queued % ring));
+      if (dev_ok) ++queued;
+    }
+    if (k >= queued) break;
+    dev_ok = landed(static_cast<int>(k % ring)) && dev_ok;
+    if (dev_ok && io_ok) io_ok = sink(k, static_cast<int>(k % ring));
+  }
+  return !dev_ok ? SL_EHIP : !io_ok ? SL_EIO : SL_OK;
+}
+
+bool put_all(int fd, const char* p, size_t len) {
+  while (len) {
+    const ssize_t w = write(fd, p, len);
+    if (w < 0 && errno == EINTR) continue;
+    if (w <= 0) return false;
+    p += w;
+    len -= static_cast<size_t>(w);
+  }
+  return true;
+}
+
+double ms_since(std::chrono::steady_clock::time_point t0) {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+bool bad_mesh(const double* vertices, int64_t n_v, const int32_t* triangles, int64_t n_t) {
+  return n_v < 0 || n_t < 0 || n_v >= (1ll << 31) || n_t >= (1ll << 31) || (n_v && !vertices) || (n_t && !triangles);
+}
+
+// chunk_triangles: 0 the default, else rounded up to whole workgroups; -1 when out of range
+int64_t chunk_of(int64_t chunk_triangles) {
+  if (chunk_triangles == 0) return kChunkTriangles;
+  if (chunk_triangles < 0 || chunk_triangles > kMaxChunkTriangles) return -1;
+  return (chunk_triangles + kT - 1) / kT * kT;
+}
+
+// sums[v][c] of the header (zeroed here) on `s`
+int vertex_sums(sl_ctx* c, const double* vertices, int64_t n_v, const int32_t* triangles, int64_t n_t, int64_t* sums,
+                hipStream_t s) {
+  if (n_v) MTRY(c, hipMemsetAsync(sums, 0, sizeof(int64_t) * 3 * static_cast<size_t>(n_v), s));
+  if (n_t)
+    hipLaunchKernelGGL(k_mw_vn_add, dim3(blocks(n_t)), dim3(kT), 0, s, vertices, triangles, n_t,
+                       reinterpret_cast<unsigned long long*>(sums));
+  MTRY(c, hipGetLastError());
+  return SL_OK;
+}
+
+// The file (path NULL: no file, everything else the same -- a measurement aid): `head`, then the chunks.
+// pack(k, dev): chunk k's kernels onto `s`; bytes(k): its size.
+template <class Pack, class Bytes>
+int write_chunks(sl_ctx* c, const char* what, const char* path, const char* head, size_t head_len, Ring* ring,
+                 int64_t n_chunks, Pack pack, Bytes bytes, hipStream_t s) {
+  const auto t_all = std::chrono::steady_clock::now();
+  const int fd = path ? slgpu_open_replacing(path) : -1;
+  if (path && fd < 0) return slgpu_fail(c, SL_EIO, (std::string(what) + ": cannot open the file").c_str());
+  bool io_ok = !path || put_all(fd, head, head_len);
+  const int r = stream_chunks(
+      io_ok ? n_chunks : 0, kRing,
+      [&](int64_t k, int slot) {
+        pack(k, ring->dev[slot]);
+        return hipGetLastError() == hipSuccess &&
+               hipMemcpyAsync(ring->pin[slot], ring->dev[slot], static_cast<size_t>(bytes(k)), hipMemcpyDeviceToHost,
+                              s) == hipSuccess &&
+               hipEventRecord(ring->ev[slot], s) == hipSuccess;
+      },
+      [&](int slot) {
+        const auto t0 = std::chrono::steady_clock::now();
+        const bool ok = hipEventSynchronize(ring->ev[slot]) == hipSuccess;
+        tls_ms[0] += ms_since(t0);
+        return ok;
+      },
+      [&](int64_t k, int slot) {
+        if (!path) return true;
+        const auto t0 = std::chrono::steady_clock::now();
+        const bool ok = put_all(fd, ring->pin[slot], static_cast<size_t>(bytes(k)));
+        tls_ms[1] += ms_since(t0);
+        return ok;
+      });
+  if (r == SL_EHIP) (void)hipStreamSynchronize(s);  // a half-queued chunk may still be writing its slot
+  if (fd >= 0) io_ok = (close(fd) == 0) && io_ok;
+  tls_ms[2] = ms_since(t_all);
+  if (r == SL_EHIP) return slgpu_fail(c, SL_EHIP, (std::string(what) + ": packing or copying failed").c_str());
+  if (r == SL_EIO || !io_ok) return slgpu_fail(c, SL_EIO, (std::string(what) + ": writing the file failed").c_str());
+  return SL_OK;
+}
+
+}  // namespace mwr
+}  // namespace
+
+extern "C" {
+
+int sl_mesh_triangle_normals(sl_ctx* c, const double* vertices, int64_t n_vertices, const int32_t* triangles,
+                             int64_t n_triangles, double* out, void* stream) {
+  using namespace mwr;
+  if (!c) return SL_EINVAL;
+  if (bad_mesh(vertices, n_vertices, triangles, n_triangles) || (n_triangles && !out))
+    return slgpu_fail(c, SL_EINVAL, "sl_mesh_triangle_normals: bad sizes or NULL arguments");
+  if (n_triangles == 0) return SL_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  PoolStream pool_stream(s);
+  MTRY(c, hipSetDevice(slgpu_device(c)));
+  int r = mcl::require_indices(c, triangles, n_triangles, n_vertices,
+                               "sl_mesh_triangle_normals: triangle index out of range", s);
+  if (r) return r;
+  hipLaunchKernelGGL(k_mw_tri_normals, dim3(blocks(n_triangles)), dim3(kT), 0, s, vertices, triangles, n_triangles,
+                     out);
+  MTRY(c, hipGetLastError());
+  MTRY(c, hipStreamSynchronize(s));
+  return SL_OK;
+}
+
+int sl_mesh_vertex_normals(sl_ctx* c, const double* vertices, int64_t n_vertices, const int32_t* triangles,
+                           int64_t n_triangles, double* out, void* stream) {
+  using namespace mwr;
+  if (!c) return SL_EINVAL;
+  if (bad_mesh(vertices, n_vertices, triangles, n_triangles) || (n_vertices && !out))
+    return slgpu_fail(c, SL_EINVAL, "sl_mesh_vertex_normals: bad sizes or NULL arguments");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  PoolStream pool_stream(s);
+  MTRY(c, hipSetDevice(slgpu_device(c)));
+  int r = mcl::require_indices(c, triangles, n_triangles, n_vertices,
+                               "sl_mesh_vertex_normals: triangle index out of range", s);
+  if (r) return r;
+  if (n_vertices == 0) return SL_OK;
+  DBuf<int64_t> sums;
+  MTRY(c, sums.alloc(3 * n_vertices));
+  r = vertex_sums(c, vertices, n_vertices, triangles, n_triangles, sums.p, s);
+  if (r) return r;
+  hipLaunchKernelGGL(k_mw_vn_norm, dim3(blocks(n_vertices)), dim3(kT), 0, s, sums.p, n_vertices, out);
+  MTRY(c, hipGetLastError());
+  MTRY(c, hipStreamSynchronize(s));
+  return SL_OK;
+}
+
+int sl_write_stl_device(sl_ctx* c, const char* path, const double* vertices, int64_t n_vertices,
+                        const int32_t* triangles, int64_t n_triangles, int64_t chunk_triangles, void* stream) {
+  using namespace mwr;
+  if (!c) return SL_EINVAL;
+  const int64_t chunk = chunk_of(chunk_triangles);
+  if (bad_mesh(vertices, n_vertices, triangles, n_triangles) || chunk < 0)
+    return slgpu_fail(c, SL_EINVAL, "sl_write_stl_device: bad sizes or NULL arguments");
+  for (double& v : tls_ms) v = 0.0;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  PoolStream pool_stream(s);
+  MTRY(c, hipSetDevice(slgpu_device(c)));
+  int r = mcl::require_indices(c, triangles, n_triangles, n_vertices, "sl_write_stl_device: triangle index out of range",
+                               s);
+  if (r) return r;
+  Ring* ring = nullptr;
+  r = ring_reserve(c, chunk * kStlRec, &ring);
+  if (r) return r;
+  char head[84] = {};
+  const uint32_t count = static_cast<uint32_t>(n_triangles);
+  memcpy(head + 80, &count, 4);
+  const int64_t n_chunks = (n_triangles + chunk - 1) / chunk;
+  auto in_chunk = [&](int64_t k) { return std::min(chunk, n_triangles - k * chunk); };
+  return write_chunks(
+      c, "sl_write_stl_device", path, head, sizeof(head), ring, n_chunks,
+      [&](int64_t k, char* dev) {
+        hipLaunchKernelGGL(k_mw_pack_stl, dim3(blocks(in_chunk(k))), dim3(kT), 0, s, vertices, triangles, k * chunk,
+                           in_chunk(k), reinterpret_cast<uint4*>(dev));
+      },
+      [&](int64_t k) { return in_chunk(k) * kStlRec; }, s);
+}
+
+int sl_write_mesh_ply_device(sl_ctx* c, const char* path, const double* vertices, int64_t n_vertices,
+                             const int32_t* triangles, int64_t n_triangles, int64_t chunk_triangles, void* stream) {
+  using namespace mwr;
+  if (!c) return SL_EINVAL;
+  const int64_t chunk = chunk_of(chunk_triangles);
+  if (bad_mesh(vertices, n_vertices, triangles, n_triangles) || chunk < 0)
+    return slgpu_fail(c, SL_EINVAL, "sl_write_mesh_ply_device: bad sizes or NULL arguments");
+  for (double& v : tls_ms) v = 0.0;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  PoolStream pool_stream(s);
+  MTRY(c, hipSetDevice(slgpu_device(c)));
+  int r = mcl::require_indices(c, triangles, n_triangles, n_vertices,
+                               "sl_write_mesh_ply_device: triangle index out of range", s);
+  if (r) return r;
+  Ring* ring = nullptr;
+  r = ring_reserve(c, chunk * kStlRec, &ring);  // the slots of the STL writer: chunk faces or chunk 50 / 48 vertices
+  if (r) return r;
+  DBuf<int64_t> sums;
+  MTRY(c, sums.alloc(3 * n_vertices));
+  r = vertex_sums(c, vertices, n_vertices, triangles, n_triangles, sums.p, s);
+  if (r) return r;
+  char head[512];
+  const int hl = snprintf(head, sizeof(head),
+                          "ply\nformat binary_little_endian 1.0\ncomment Created by Open3D\nelement vertex %lld\n"
+                          "property double x\nproperty double y\nproperty double z\n"
+                          "property double nx\nproperty double ny\nproperty double nz\n"
+                          "element face %lld\nproperty list uchar uint vertex_indices\nend_header\n",
+                          static_cast<long long>(n_vertices), static_cast<long long>(n_triangles));
+  const int64_t vchunk = chunk * kStlRec / kVertexRec;
+  const int64_t nvc = (n_vertices + vchunk - 1) / vchunk, nfc = (n_triangles + chunk - 1) / chunk;
+  auto v_in = [&](int64_t k) { return std::min(vchunk, n_vertices - k * vchunk); };
+  auto f_in = [&](int64_t k) { return std::min(chunk, n_triangles - k * chunk); };
+  return write_chunks(
+      c, "sl_write_mesh_ply_device", path, head, static_cast<size_t>(hl), ring, nvc + nfc,
+      [&](int64_t k, char* dev) {
+        if (k < nvc)
+          hipLaunchKernelGGL(k_mw_pack_vertices, dim3(blocks(6 * v_in(k))), dim3(kT), 0, s, vertices, sums.p,
+                             k * vchunk, v_in(k), reinterpret_cast<double*>(dev));
+        else
+          hipLaunchKernelGGL(k_mw_pack_faces, dim3(blocks(f_in(k - nvc))), dim3(kT), 0, s, triangles,
+                             (k - nvc) * chunk, f_in(k - nvc), reinterpret_cast<uint4*>(dev));
+      },
+      [&](int64_t k) { return k < nvc ? v_in(k) * kVertexRec : f_in(k - nvc) * kFaceRec; }, s);
+}
+
+int sl_mesh_write_stats(double* stage_ms, int capacity) {
+  using namespace mwr;
+  if (capacity < 0 || (capacity && !stage_ms)) return SL_EINVAL;
+  for (int i = 0; i < capacity; ++i) stage_ms[i] = i < 3 ? tls_ms[i] : 0.0;
+  return SL_OK;
+}
+
+}  // extern "C"

@@ -35,6 +35,13 @@ tests/meshclean_oracle.py is their CPU form, which the results equal exactly).
 The drop-ins apply them when asked to (``keep_largest_component``,
 ``min_component_triangles``, ``simplify_voxel_size``).
 
+``write_triangle_mesh`` writes the mesh as ``.stl`` or ``.ply``: device tensors
+are packed into records by HIP kernels and streamed to the file through a ring
+of two pinned chunks (csrc/slmeshwrite.inl states the arithmetic and the
+layout); ``compute_triangle_normals`` and ``compute_vertex_normals`` are the
+normals it writes (the vertex normals as order-free fixed-point sums; exact
+against tests/meshwrite_oracle.py).
+
 Open3D's Poisson is the adaptive-octree variant and is not installed here:
 parity with Open3D is unpinned, and tests/mesh_oracle.py is the CPU restatement
 the tests check against -- bit for bit for every stage except the solve.
@@ -673,31 +680,144 @@ def _host(a, dtype):
     return np.ascontiguousarray(np.asarray(a, dtype=dtype)).reshape(-1, 3)
 
 
+def _mesh_args(vertices, triangles, device):
+    eng = _engine(device)
+    V = _f64(vertices, eng.device)
+    T = _tris(triangles, eng.device)
+    return eng, V, T
+
+
+def compute_triangle_normals(vertices, triangles, *, device=None) -> torch.Tensor:
+    """TriangleMesh.compute_triangle_normals -> f64 [T, 3] on the device: (p1 - p0)
+    x (p2 - p0) over its length, zero for a zero-area triangle -- the arithmetic
+    of the STL writer, bit for bit (csrc/slmeshwrite.inl states it).  An index
+    outside 0 .. V - 1 raises IndexError."""
+    eng, V, T = _mesh_args(vertices, triangles, device)
+    out = torch.empty((max(len(T), 1), 3), dtype=torch.float64, device=eng.device)
+    _call(eng, "sl_mesh_triangle_normals", _ptr(V) if len(V) else None, len(V), _ptr(T) if len(T) else None, len(T),
+          _ptr(out))
+    return out[: len(T)]
+
+
+def compute_vertex_normals(vertices, triangles, *, device=None) -> torch.Tensor:
+    """TriangleMesh.compute_vertex_normals -> f64 [V, 3] on the device: the unit
+    normals of a vertex's triangles summed and normalised; (0, 0, 1) for a
+    vertex of no triangle or one whose normals cancel.  Deviation: Open3D adds
+    in f64 in triangle order; here every triangle adds llrint(n 2^40) to 64-bit
+    integer sums, so the result depends on no order and repeats
+    (csrc/slmeshwrite.inl; exact against tests/meshwrite_oracle.py).  An index
+    outside 0 .. V - 1 raises IndexError."""
+    eng, V, T = _mesh_args(vertices, triangles, device)
+    out = torch.empty((max(len(V), 1), 3), dtype=torch.float64, device=eng.device)
+    _call(eng, "sl_mesh_vertex_normals", _ptr(V) if len(V) else None, len(V), _ptr(T) if len(T) else None, len(T),
+          _ptr(out))
+    return out[: len(V)]
+
+
+def mesh_write_stats(*, device=None) -> dict:
+    """Host milliseconds of this thread's last device write (sl_mesh_write_stats; a
+    measurement aid): waiting for packed chunks to land, inside write(), in all."""
+    eng = _engine(device)
+    v = (ctypes.c_double * 3)()
+    _lib.check(eng._L.sl_mesh_write_stats(v, 3), None, "sl_mesh_write_stats")
+    return {"wait_ms": v[0], "write_ms": v[1], "total_ms": v[2]}
+
+
 _STL_REC = np.dtype([("normal", "<f4", 3), ("v", "<f4", (3, 3)), ("attr", "<u2")])
+_PLY_FACE = np.dtype([("n", "u1"), ("v", "<u4", 3)])
+_VN_FIX = 2.0 ** 40
+_MESH_EXTS = (".stl", ".ply")
 
 
-def write_triangle_mesh(path, vertices, triangles) -> None:
-    """o3d.io.write_triangle_mesh for ``.stl``: binary STL (80-byte header, the
-    count, per triangle the unit normal, three vertices and a zero attribute,
-    float32).  Normals are taken in f64 from the f64 vertices; a zero-area
-    triangle gets a zero normal."""
-    if os.path.splitext(str(path))[1].lower() != ".stl":
-        raise ValueError(f"cannot write {path}: only .stl is supported")
-    P = _host(vertices, np.float64)
-    T = _host(triangles, np.int64)
-    if len(T) and (T.min() < 0 or T.max() >= len(P)):
-        raise IndexError("triangle index out of range")
+def _mesh_ply_header(n_vertices: int, n_triangles: int) -> bytes:
+    return (f"ply\nformat binary_little_endian 1.0\ncomment Created by Open3D\nelement vertex {n_vertices}\n"
+            "property double x\nproperty double y\nproperty double z\n"
+            "property double nx\nproperty double ny\nproperty double nz\n"
+            f"element face {n_triangles}\nproperty list uchar uint vertex_indices\nend_header\n").encode("ascii")
+
+
+def _host_triangle_normals(P, T):
     p0, p1, p2 = P[T[:, 0]], P[T[:, 1]], P[T[:, 2]]
     e1, e2 = p1 - p0, p2 - p0
     n = np.stack([e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1], e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2],
                   e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]], 1)
     ln = np.sqrt((n[:, 0] * n[:, 0] + n[:, 1] * n[:, 1]) + n[:, 2] * n[:, 2])
     with np.errstate(invalid="ignore", divide="ignore"):
-        n = np.where((ln == 0.0)[:, None], 0.0, n / ln[:, None])
+        return np.where((ln == 0.0)[:, None], 0.0, n / ln[:, None])
+
+
+def _host_vertex_normals(P, T):
+    """compute_vertex_normals in NumPy: the same fixed-point sums (int64, wrapping)."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        t = _host_triangle_normals(P, T) * _VN_FIX
+        q = np.rint(np.where(np.abs(t) < 2.0 ** 62, t, 0.0)).astype(np.int64)
+    acc = np.zeros((len(P), 3), dtype=np.int64)
+    for j in range(3):
+        np.add.at(acc, T[:, j], q)
+    s = acc.astype(np.float64)
+    ln = np.sqrt((s[:, 0] * s[:, 0] + s[:, 1] * s[:, 1]) + s[:, 2] * s[:, 2])
+    zero = ~s.any(1)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out = s / ln[:, None]
+    out[zero] = (0.0, 0.0, 1.0)
+    return out
+
+
+def _write_host(path, ext, vertices, triangles):
+    P = _host(vertices, np.float64)
+    T = _host(triangles, np.int64)
+    if len(T) and (T.min() < 0 or T.max() >= len(P)):
+        raise IndexError("triangle index out of range")
+    if ext == ".ply":
+        rec = np.zeros(len(T), dtype=_PLY_FACE)
+        rec["n"] = 3
+        rec["v"] = T
+        with open(path, "wb") as f:
+            f.write(_mesh_ply_header(len(P), len(T)))
+            np.concatenate([P, _host_vertex_normals(P, T)], 1).astype("<f8").tofile(f)
+            rec.tofile(f)
+        return
+    p0, p1, p2 = P[T[:, 0]], P[T[:, 1]], P[T[:, 2]]
     rec = np.zeros(len(T), dtype=_STL_REC)
-    rec["normal"] = n
-    rec["v"][:, 0], rec["v"][:, 1], rec["v"][:, 2] = p0, p1, p2
+    rec["normal"] = _host_triangle_normals(P, T)
+    with np.errstate(over="ignore"):  # beyond float32: +-inf, as the cast says
+        rec["v"][:, 0], rec["v"][:, 1], rec["v"][:, 2] = p0, p1, p2
     with open(path, "wb") as f:
         f.write(b"\0" * 80)
         f.write(np.uint32(len(T)).tobytes())
         rec.tofile(f)
+
+
+def _write_device(path, ext, vertices, triangles, chunk_triangles=0):
+    """The device writers (csrc/slmeshwrite.inl).  ``path`` None: packed and copied back, no file (measurement)."""
+    eng, V, T = _mesh_args(vertices, triangles, vertices.device)
+    name = "sl_write_mesh_ply_device" if ext == ".ply" else "sl_write_stl_device"
+    try:
+        _call(eng, name, None if path is None else os.fsencode(path), _ptr(V) if len(V) else None, len(V),
+              _ptr(T) if len(T) else None, len(T), int(chunk_triangles))
+    except IndexError:
+        raise IndexError("triangle index out of range") from None
+
+
+def write_triangle_mesh(path, vertices, triangles, *, chunk_triangles: int = 0) -> None:
+    """o3d.io.write_triangle_mesh for ``.stl`` and ``.ply``, after the
+    reference's compute_vertex_normals().  ``.stl``: binary STL (80-byte header,
+    the count, per triangle the unit normal, three vertices and a zero attribute,
+    float32); normals are taken in f64 from the f64 vertices, and a zero-area
+    triangle gets a zero normal.  ``.ply``: Open3D's binary little-endian layout
+    (unpinned) -- per vertex six doubles, position and ``compute_vertex_normals``;
+    per face the byte 3 and three uint32 -- which keeps the shared vertices.
+    Two CUDA tensors on one device are packed on that device and streamed to the
+    file through a ring of two pinned chunks of ``chunk_triangles`` triangles (0:
+    655 360); anything else (NumPy, CPU tensors) is packed on the host in NumPy.
+    Both routes write the same bytes.  An index outside 0 .. V - 1 raises
+    IndexError before the path is opened; another extension raises ValueError."""
+    ext = os.path.splitext(str(path))[1].lower()
+    if ext not in _MESH_EXTS:
+        raise ValueError(f"cannot write {path}: only .stl and .ply are supported")
+    on_device = (isinstance(vertices, torch.Tensor) and isinstance(triangles, torch.Tensor) and vertices.is_cuda
+                 and triangles.is_cuda and vertices.device == triangles.device)
+    if on_device:
+        _write_device(str(path), ext, vertices, triangles, chunk_triangles)
+    else:
+        _write_host(path, ext, vertices, triangles)
