@@ -773,6 +773,17 @@ int sl_ball_pivot_candidates_stats(double* stats, int capacity);
  * the bytes released -> *released_bytes (may be NULL). */
 int sl_merge_pool_trim(int device, int64_t* released_bytes);
 
+/* Test aid: poison the merge pool's scratch.  byte 0..255 arms the mode: every
+ * buffer the pool hands out from then on (reused or fresh) has the bytes that
+ * were asked for filled with that value, on the stream of the entry point
+ * that asked, before that entry point's first kernel; -1 disarms it (the
+ * default); anything else is SL_EINVAL and changes nothing.  The bytes
+ * filled so far in this process, never reset -> *poisoned_bytes (may be NULL).
+ * Results must not depend on the mode: a difference is a word read before it
+ * is written.  The context-owned scratch of the decode path and of the PLY
+ * reader and writer is not pooled and not covered. */
+int sl_merge_pool_poison(int byte, int64_t* poisoned_bytes);
+
 /* ---- multi-GPU gather ----
  * The merge's one exchange: every rank's cloud to `root` in rank order over
  * RCCL (opened with dlopen by soname, so a process that already holds

@@ -46,7 +46,7 @@ EXPORTS = ("sl_abi_version", "sl_ctx_create", "sl_ctx_destroy", "sl_ctx_last_err
            "sl_last_thresholds", "sl_last_launch_info", "sl_profile_enable", "sl_profile_read", "sl_time_kernels", "sl_format_ply", "sl_write_ply",
            "sl_write_ply_device", "sl_write_ply_binary", "sl_voxel_downsample", "sl_statistical_outliers", "sl_select_by_index",
            "sl_transform_points", "sl_estimate_normals", "sl_icp_point_to_plane", "sl_radius_search", "sl_compute_fpfh",
-           "sl_feature_nn", "sl_ransac_feature_matching", "sl_segment_plane", "sl_index_complement", "sl_merge_pool_trim", "sl_calib_products", "sl_gather_unique_id", "sl_gather_init", "sl_gather_counts",
+           "sl_feature_nn", "sl_ransac_feature_matching", "sl_segment_plane", "sl_index_complement", "sl_merge_pool_trim", "sl_merge_pool_poison", "sl_calib_products", "sl_gather_unique_id", "sl_gather_init", "sl_gather_counts",
            "sl_gather",
            "sl_mesh_splat", "sl_mesh_unfix", "sl_mesh_divergence", "sl_mesh_sample", "sl_ordered_sum",
            "sl_orient_normals", "sl_mesh_extract_count", "sl_mesh_extract_emit", "sl_mesh_remove_vertices",
@@ -115,6 +115,7 @@ _SIGS = {
                                 ctypes.POINTER(_i32), _vp]),
     "sl_index_complement": (_i32, [_vp, _vp, _i64, _i64, _vp, ctypes.POINTER(_i64), _vp]),
     "sl_merge_pool_trim": (_i32, [_i32, ctypes.POINTER(_i64)]),
+    "sl_merge_pool_poison": (_i32, [_i32, ctypes.POINTER(_i64)]),
     "sl_mesh_splat": (_i32, [_vp, _vp, _vp, _i64, _i32, ctypes.POINTER(ctypes.c_double), ctypes.c_double, _vp, _vp]),
     "sl_mesh_unfix": (_i32, [_vp, _vp, _i64, _vp, _vp]),
     "sl_mesh_divergence": (_i32, [_vp, _vp, _i32, ctypes.c_double, _vp, _vp]),

@@ -28,6 +28,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <atomic>
 #include <limits>
 #include <map>
 #include <mutex>
@@ -1346,6 +1347,19 @@ struct PoolStream {  // RAII: the stream the entry point's scratch is used on
   ~PoolStream() { tls_stream = prev; }
 };
 
+// Test aid (sl_merge_pool_poison): while armed (0..255), every buffer the pool
+// hands out has its requested bytes filled with that value on the entry
+// point's stream, so a word read before it is written shows in the result.
+std::atomic<int> g_poison_byte{-1};
+std::atomic<int64_t> g_poisoned_bytes{0};
+
+hipError_t pool_poison(void* p, size_t bytes) {
+  const int byte = g_poison_byte.load(std::memory_order_relaxed);
+  if (byte < 0) return hipSuccess;
+  g_poisoned_bytes.fetch_add(static_cast<int64_t>(bytes), std::memory_order_relaxed);
+  return hipMemsetAsync(p, byte, bytes, tls_stream);
+}
+
 hipError_t pool_alloc(void** out, size_t bytes) {
   int dev = 0;
   hipError_t e = hipGetDevice(&dev);
@@ -1358,10 +1372,11 @@ hipError_t pool_alloc(void** out, size_t bytes) {
       *out = it->second.second;
       P.cached[dev] -= it->first;
       P.free.erase(it);
-      return hipSuccess;
+      return pool_poison(*out, bytes);
     }
   }
-  return hipMalloc(out, bytes);
+  e = hipMalloc(out, bytes);
+  return e != hipSuccess ? e : pool_poison(*out, bytes);
 }
 
 // ptr must be idle (its stream synchronised)
@@ -2163,6 +2178,16 @@ int sl_merge_pool_trim(int device, int64_t* released_bytes) {
   const size_t b = pool_trim(device);
   (void)hipSetDevice(prev);
   if (released_bytes) *released_bytes = static_cast<int64_t>(b);
+  return SL_OK;
+}
+
+// Test aid: byte 0..255 arms the scratch pool's poison fill (every buffer it
+// hands out is filled with that value on the entry point's stream), -1 disarms
+// it; the bytes filled so far, never reset -> *poisoned_bytes (may be NULL).
+int sl_merge_pool_poison(int byte, int64_t* poisoned_bytes) {
+  if (byte < -1 || byte > 255) return SL_EINVAL;
+  g_poison_byte.store(byte, std::memory_order_relaxed);
+  if (poisoned_bytes) *poisoned_bytes = g_poisoned_bytes.load(std::memory_order_relaxed);
   return SL_OK;
 }
 

@@ -531,6 +531,51 @@ def pool_trim(device=None) -> int:
     return out.value
 
 
+_poison_lock = threading.Lock()
+_poison_mode = -1  # the mode this module last set: -1 disarmed, else the byte
+
+
+def _pool_poison_set(byte: int) -> int:
+    """sl_merge_pool_poison(byte) -> the counter; the mode set is remembered.  Under _poison_lock."""
+    global _poison_mode
+    out = ctypes.c_int64()
+    _lib.check(_lib.load().sl_merge_pool_poison(byte, ctypes.byref(out)), None,
+               "sl_merge_pool_poison: byte must be 0..255, or -1 to disarm")
+    _poison_mode = byte
+    return out.value
+
+
+class pool_poison:
+    """Test aid (sl_merge_pool_poison): ``with merge.pool_poison(0xFF) as p:`` fills every scratch buffer
+    the merge pool hands out inside the block with that byte before its entry point's first kernel; when
+    the block ends the mode is what it was before it (disarmed, or an outer block's byte).  ``p.bytes()``
+    is the process-wide count of bytes filled so far (never reset: use differences); reading it, inside or
+    outside a block, leaves the mode alone (the C call reports the counter only while setting a mode, so
+    the mode this module set last is set again: a mode set past this module, through ctypes, is not
+    known here).  The mode is process-wide: blocks in several threads at once are not supported.
+    Results must not depend on any of it."""
+
+    def __init__(self, byte: int):
+        self.byte = int(byte)
+        self._before = -1
+
+    def bytes(self) -> int:
+        with _poison_lock:
+            return _pool_poison_set(_poison_mode)
+
+    def __enter__(self):
+        with _poison_lock:
+            before = _poison_mode
+            _pool_poison_set(self.byte)  # ValueError for a byte outside 0..255: nothing changes
+            self._before = before
+        return self
+
+    def __exit__(self, *exc):
+        with _poison_lock:
+            _pool_poison_set(self._before)
+        return False
+
+
 def postprocess(points, colors, voxel_size: float, nb_neighbors: int = 20, std_ratio: float = 2.0, *,
                 device=None):
     """processing.py:171-175: voxel_down_sample, then remove_statistical_outlier + select_by_index."""
