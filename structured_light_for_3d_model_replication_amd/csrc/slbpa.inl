@@ -1,6 +1,7 @@
 // libslgpu.so, part 2h -- ball-pivoting surface meshing, included at the end of
 // slmerge.hip (one translation unit: it shares that file's scratch pool, scan,
-// radix sort and search grid).  The reference's reconstruct_stl(mode="surface")
+// triple sort and search grid, and slprim.inl's finite check and stage clock).
+// The reference's reconstruct_stl(mode="surface")
 // (server/processing.py:220-237) is Open3D's create_from_point_cloud_ball_pivoting,
 // a sequential front that pivots one edge at a time.  It is restated here in an
 // order-free form: the surface a ball of radius r can roll over is the set of
@@ -76,8 +77,9 @@
 // tests the staged neighbourhood as blockers 64 at a time and leaves at the first
 // hit.  What is left is appended through one atomic per batch to a capacity
 // buffer (the count goes on past the capacity: the caller re-runs with the exact
-// size), and two stable radix sorts (by k, then by i n + j) bring the output into
-// rank order, so two runs give identical arrays.  All loop bounds are
+// size), and slmerge.hip's sort_triples (two stable radix sorts: by k, then by i n
+// + j, the flip bit masked off i) brings the output into rank order, so two runs
+// give identical arrays.  All loop bounds are
 // wave-uniform.
 
 namespace {
@@ -274,22 +276,7 @@ __global__ __launch_bounds__(kW) void k_bpa(SearchGrid sg, const int64_t* live, 
   }
 }
 
-// the keys of the two ordering sorts: k of raw[t]; (i n + j) of raw[perm[t]]
-__global__ __launch_bounds__(kT) void k_bpa_key_k(const uint32_t* raw, int64_t m, uint64_t* key, uint32_t* perm) {
-  const int64_t t = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
-  if (t >= m) return;
-  key[t] = raw[3 * t + 2];
-  perm[t] = static_cast<uint32_t>(t);
-}
-
-__global__ __launch_bounds__(kT) void k_bpa_key_ij(const uint32_t* raw, const uint32_t* perm, int64_t m, uint64_t n,
-                                                   uint64_t* key) {
-  const int64_t t = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
-  if (t >= m) return;
-  const int64_t s = perm[t];
-  key[t] = static_cast<uint64_t>(raw[3 * s] & ~kInner) * n + raw[3 * s + 1];
-}
-
+// raw[perm[t]] with its flip bit applied: the winding
 __global__ __launch_bounds__(kT) void k_bpa_emit(const uint32_t* raw, const uint32_t* perm, int64_t m, int32_t* tri) {
   const int64_t t = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
   if (t >= m) return;
@@ -324,9 +311,9 @@ int sl_ball_pivot_candidates(sl_ctx* c, const double* xyz, const double* normals
   hipStream_t s = static_cast<hipStream_t>(stream);
   PoolStream pool_stream(s);
   MTRY(c, hipSetDevice(slgpu_device(c)));
-  int r = clu::require_finite(c, xyz, n, "sl_ball_pivot_candidates: non-finite point coordinates", s);
+  int r = prim::require_finite(c, xyz, n, "sl_ball_pivot_candidates: non-finite point coordinates", s);
   if (r) return r;
-  clu::StageClock clock(s);
+  prim::StageClock clock(s);
   SearchGridBufs sg;
   r = build_search_grid(c, xyz, n, 2.0 * radius, GridTable::kNeighbours,
                         "sl_ball_pivot_candidates: non-finite point coordinates", &sg, s);
@@ -387,13 +374,7 @@ int sl_ball_pivot_candidates(sl_ctx* c, const double* xyz, const double* normals
   DBuf<uint32_t> perm;
   MTRY(c, key.alloc(m));
   MTRY(c, perm.alloc(m));
-  hipLaunchKernelGGL(k_bpa_key_k, dim3(blocks(m)), dim3(kT), 0, s, raw.p, m, key.p, perm.p);
-  MTRY(c, hipGetLastError());
-  r = radix_sort(c, key.p, perm.p, m, key_bits(static_cast<uint64_t>(n - 1)), s);
-  if (r) return r;
-  hipLaunchKernelGGL(k_bpa_key_ij, dim3(blocks(m)), dim3(kT), 0, s, raw.p, perm.p, m, static_cast<uint64_t>(n), key.p);
-  MTRY(c, hipGetLastError());
-  r = radix_sort(c, key.p, perm.p, m, key_bits(static_cast<uint64_t>(n) * static_cast<uint64_t>(n) - 1), s);
+  r = sort_triples(c, raw.p, m, static_cast<uint64_t>(n), ~kInner, key.p, perm.p, s);  // rank order
   if (r) return r;
   hipLaunchKernelGGL(k_bpa_emit, dim3(blocks(m)), dim3(kT), 0, s, raw.p, perm.p, m, triangles);
   MTRY(c, hipGetLastError());

@@ -1,6 +1,7 @@
 // libslgpu.so, part 2g -- density clustering for the per-view clean-up, included
 // at the end of slmerge.hip (one translation unit: it shares that file's scratch
-// pool, scan, search grid and kNN pyramid).  The reference's second cleaning
+// pool, scan, search grid and kNN pyramid, and slprim.inl's union-find, fold_min,
+// finite check and stage clock).  The reference's second cleaning
 // recipe (Old/StatisticalOutlierRemoval.py, remove_outliers_keep_color2) is
 // compute_nearest_neighbor_distance, cluster_dbscan(eps, min_points) + "keep the
 // largest cluster", and remove_radius_outlier(nb_points, radius): Open3D calls.
@@ -45,38 +46,23 @@
 // POSITION (a tile's words are then one contiguous read; indexed by point index
 // the two gathers per candidate were most of the pass) and starts as the
 // identity.  One traversal unites every core point with its core neighbours of
-// lower position (every edge is seen from its later end).  A root is hooked
-// under a SMALLER root by atomicCAS(parent[a], a, b), b < a, and only roots are
-// hooked, so parents only decrease, no cycle can form, and a component's final
-// root is its smallest core position whatever the interleaving.  Path halving
-// lowers a non-root's parent to an ancestor by atomicMin.  The cluster's
-// smallest core INDEX, which the labels rank, is one atomicMin per core point
-// into its root's slot after the unions.
-// Stale reads.  Within a launch the L1s and the per-XCD L2s are not coherent;
-// parent words are read by agent-scope relaxed atomic loads, and even those may
-// return an older value.  An older value of parent[x] is x itself or an older
-// ancestor of x (a word only ever moves down its own ancestor chain), so:
-//   - find() walks strictly decreasing indices and ends at a point that WAS a
-//     root: no wait, no spin;
-//   - a hook on a point that is no longer a root fails its CAS, which returns
-//     the true parent, and the loop continues from THAT value (never from a
-//     plain re-read), so every retry is strictly lower: progress without
-//     waiting on another workgroup;
-//   - "both ends share an ancestor" (the test that skips the distance
-//     computation) is true of stale ancestors only if it is true: ancestors are
-//     never un-made.
-// A stale read therefore costs steps and never a wrong union; the atomics
-// themselves act on the one copy at the device's coherence point.  After the
-// launch (a kernel boundary makes everything visible) the trees are walked with
-// plain loads to the roots, each root's smallest point index is found and those
-// are ranked by the flag / scan passes, and a second traversal gives every
-// border point its minimum core label.  Nothing on the host iterates until
-// convergence.
-
-#include <time.h>
+// lower position (every edge is seen from its later end).  The union-find is
+// slprim.inl's (find_root / unite), and that file's header holds the argument
+// that it is wait-free and that a stale read of a parent word costs steps and
+// never a wrong union; a component's final root is its smallest core position
+// whatever the interleaving.  Here "both ends share an ancestor" is the test
+// that skips the distance computation.  The cluster's smallest core INDEX,
+// which the labels rank, is one atomicMin per core point into its root's slot
+// after the unions.  After the launch (a kernel boundary makes everything
+// visible) the trees are walked with plain loads to the roots, each root's
+// smallest point index is found and those are ranked by the flag / scan
+// passes, and a second traversal gives every border point its minimum core
+// label.  Nothing on the host iterates until convergence.
 
 namespace {
 namespace clu {
+
+using prim::find_root, prim::ld_parent, prim::unite, prim::k_clu_init, prim::require_finite, prim::StageClock;
 
 constexpr int kW = 64;     // one wave per workgroup
 constexpr int kTile = 256;  // candidates staged per pass (8 KB of LDS with the two words per candidate)
@@ -86,49 +72,6 @@ constexpr int kNoLabel = 0x7fffffff;
 enum Mode { kCount = 0, kUnion = 1, kBorder = 2 };
 
 thread_local double tls_ms[5];  // grid, count, union, flatten + rank, border of the last sl_cluster_dbscan
-
-__device__ __forceinline__ uint32_t ld_parent(const uint32_t* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// A point that is (or, read stale, was) the root of x's tree; halves the path.
-__device__ __forceinline__ uint32_t find_root(uint32_t* parent, uint32_t x) {
-  for (;;) {
-    const uint32_t p = ld_parent(parent + x);
-    if (p == x) return x;
-    const uint32_t g = ld_parent(parent + p);
-    if (g == p) return p;
-    atomicMin(parent + x, g);  // g <= p < x: an ancestor of x
-    x = g;
-  }
-}
-
-// One tree for a and b; returns a point that is an ancestor of both.
-__device__ __forceinline__ uint32_t unite(uint32_t* parent, uint32_t a, uint32_t b) {
-  for (;;) {
-    a = find_root(parent, a);
-    b = find_root(parent, b);
-    if (a == b) return a;
-    if (a < b) {
-      const uint32_t t = a;
-      a = b;
-      b = t;
-    }
-    const uint32_t old = atomicCAS(parent + a, a, b);  // the larger root under the smaller
-    if (old == a) return b;
-    a = old;  // a had been hooked already: go on from its true parent (< a)
-  }
-}
-
-__global__ __launch_bounds__(kT) void k_clu_finite(const double* xyz, int64_t n3, unsigned* bad) {
-  const int64_t i = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
-  if (i < n3 && !isfinite(xyz[i])) atomicOr(bad, 1u);
-}
-
-__global__ __launch_bounds__(kT) void k_clu_init(int64_t n, uint32_t* parent) {
-  const int64_t i = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
-  if (i < n) parent[i] = static_cast<uint32_t>(i);
-}
 
 // scnt, parent and slab are indexed by SORTED POSITION, so a tile's words are one contiguous read.
 // kCount:  min(count, lim) (lim <= 0: the count) -> out[point index] and / or out_pos[position].
@@ -264,7 +207,7 @@ __global__ __launch_bounds__(kT) void k_clu_roots(const uint32_t* parent, const 
   if (t < n) root[t] = x;
   // neighbours in position mostly share a root: one atomic per wave and root, not one per point (a
   // cluster of millions otherwise queues them all on one word).  Every lane of the wave calls.
-  ort::fold_min<uint32_t>(low, x, core ? sidx[t] : kNone, core);
+  prim::fold_min<uint32_t>(low, x, core ? sidx[t] : kNone, core);
 }
 
 // flag[i] = 1 for the point that is the smallest core index of its cluster (every i is written once).
@@ -294,38 +237,6 @@ __global__ __launch_bounds__(kT) void k_clu_scale(double* v, int64_t n, double f
 }
 
 unsigned wave_blocks(int64_t n) { return static_cast<unsigned>((n + kW - 1) / kW); }
-
-// SL_EINVAL with `msg` when a coordinate is not finite.
-int require_finite(sl_ctx* c, const double* xyz, int64_t n, const char* msg, hipStream_t s) {
-  DBuf<unsigned> bad;
-  MTRY(c, bad.alloc(1));
-  MTRY(c, hipMemsetAsync(bad.p, 0, sizeof(unsigned), s));
-  hipLaunchKernelGGL(k_clu_finite, dim3(blocks(3 * n)), dim3(kT), 0, s, xyz, 3 * n, bad.p);
-  MTRY(c, hipGetLastError());
-  unsigned h = 0;
-  MTRY(c, hipMemcpyAsync(&h, bad.p, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-  MTRY(c, hipStreamSynchronize(s));
-  return h ? slgpu_fail(c, SL_EINVAL, msg) : SL_OK;
-}
-
-// Host milliseconds of a stage, read once the stream is idle.
-struct StageClock {
-  hipStream_t s;
-  double t0;
-  static double now() {
-    timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return 1e3 * static_cast<double>(ts.tv_sec) + 1e-6 * static_cast<double>(ts.tv_nsec);
-  }
-  explicit StageClock(hipStream_t st) : s(st), t0(now()) {}
-  hipError_t lap(double* ms) {
-    const hipError_t e = hipStreamSynchronize(s);
-    const double t = now();
-    *ms = t - t0;
-    t0 = t;
-    return e;
-  }
-};
 
 }  // namespace clu
 }  // namespace

@@ -47,7 +47,7 @@ __device__ __forceinline__ int g_code(int j, int a) {
 // *flag = 1 when one of the n values is not finite.  build_search_grid's bounds
 // (fmin / fmax) see an infinity and skip a NaN, so the target is checked here
 // before any of its points is keyed into a cell.
-__global__ __launch_bounds__(kT) void k_info_nonfinite(const double* v, int64_t n, int* flag) {
+__global__ __launch_bounds__(kT) void k_info_nonfinite(const double* v, int64_t n, unsigned* flag) {
   for (int64_t i = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x; i < n;
        i += static_cast<int64_t>(gridDim.x) * kT)
     if (!isfinite(v[i])) *flag = 1;
@@ -126,20 +126,13 @@ extern "C" int sl_information_matrix(sl_ctx* c, const double* source, int64_t n_
   hipStream_t s = static_cast<hipStream_t>(stream);
   PoolStream pool_stream(s);
   MTRY(c, hipSetDevice(slgpu_device(c)));
-  {
-    DBuf<int> flag;
-    int bad = 0;
-    MTRY(c, flag.alloc(1));
-    MTRY(c, hipMemsetAsync(flag.p, 0, sizeof(int), s));
+  int r = prim::require_clear(c, SL_EINVAL, "non-finite target coordinates", s, [&](unsigned* bad) {
     const unsigned g = static_cast<unsigned>(std::min<int64_t>(2048, (3 * n_tgt + kT - 1) / kT));
-    hipLaunchKernelGGL(k_info_nonfinite, dim3(g), dim3(kT), 0, s, target, 3 * n_tgt, flag.p);
-    MTRY(c, hipGetLastError());
-    MTRY(c, hipMemcpyAsync(&bad, flag.p, sizeof(int), hipMemcpyDeviceToHost, s));
-    MTRY(c, hipStreamSynchronize(s));
-    if (bad) return slgpu_fail(c, SL_EINVAL, "non-finite target coordinates");
-  }
+    hipLaunchKernelGGL(k_info_nonfinite, dim3(g), dim3(kT), 0, s, target, 3 * n_tgt, bad);
+  });
+  if (r) return r;
   SearchGridBufs tg;
-  const int r = build_search_grid(c, target, n_tgt, max_distance, GridTable::kDense, "non-finite target coordinates",
+  r = build_search_grid(c, target, n_tgt, max_distance, GridTable::kDense, "non-finite target coordinates",
                                   &tg, s);
   if (r) return r;
   const int64_t nb = (n_src + kIcpBlock - 1) / kIcpBlock;

@@ -855,6 +855,42 @@ __global__ __launch_bounds__(kT) void k_compact_index(const uint32_t* flag, cons
   if (i < n && flag[i]) out[pos[i]] = i;
 }
 
+// keep[i] = 1 where the removal mask is clear
+__global__ __launch_bounds__(kT) void k_keep_unmasked(const uint8_t* __restrict__ mask, int64_t n,
+                                                      uint32_t* __restrict__ keep) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
+  if (i < n) keep[i] = mask[i] ? 0u : 1u;
+}
+
+// The flagged rows of in [n][W] -> out[pos[i]], pos the exclusive scan of flag.
+template <typename T, int W>
+__global__ __launch_bounds__(kT) void k_compact_rows(const T* __restrict__ in, int64_t n,
+                                                     const uint32_t* __restrict__ flag,
+                                                     const uint32_t* __restrict__ pos, T* __restrict__ out) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
+  if (i >= n || !flag[i]) return;
+  const int64_t o = pos[i];
+#pragma unroll
+  for (int a = 0; a < W; ++a) out[W * o + a] = in[W * i + a];
+}
+
+// The keys of sort_triples' two sorts: tri[j][2] with value j; then (tri[j][0] &
+// first_mask) n_index + tri[j][1] of the triples in the first sort's order.
+__global__ __launch_bounds__(kT) void k_triple_key_c(const uint32_t* tri, int64_t m, uint64_t* keys, uint32_t* vals) {
+  const int64_t j = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
+  if (j >= m) return;
+  keys[j] = tri[3 * j + 2];
+  vals[j] = static_cast<uint32_t>(j);
+}
+
+__global__ __launch_bounds__(kT) void k_triple_key_ab(const uint32_t* tri, const uint32_t* vals, int64_t m,
+                                                      uint64_t n_index, uint32_t first_mask, uint64_t* keys) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
+  if (i >= m) return;
+  const int64_t j = vals[i];
+  keys[i] = static_cast<uint64_t>(tri[3 * j] & first_mask) * n_index + tri[3 * j + 1];
+}
+
 __global__ __launch_bounds__(kT) void k_gather(const double* xyz, const uint8_t* bgr, const int64_t* idx, int64_t m,
                                                double* oxyz, uint8_t* obgr) {
   const int64_t j = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
@@ -1532,10 +1568,51 @@ bool make_grid(const double* lo, const double* hi, double h, Grid* g) {
   return true;
 }
 
+// Open3D's voxel grid over the bounds b (min[3], max[3]): voxel_min_bound = min - vs/2, voxel_max_bound = max + vs/2
+// (VoxelDownSample), with its limits and messages.
+int voxel_grid(sl_ctx* c, const double* b, double voxel_size, Grid* g) {
+  double lo[3], hi[3];
+  for (int k = 0; k < 3; ++k) {
+    lo[k] = b[k] - voxel_size * 0.5;
+    hi[k] = b[3 + k] + voxel_size * 0.5;
+  }
+  double ext = 0.0;
+  for (int k = 0; k < 3; ++k) ext = std::max(ext, hi[k] - lo[k]);
+  if (voxel_size * std::numeric_limits<int>::max() < ext) return slgpu_fail(c, SL_EINVAL, "voxel_size is too small.");
+  if (!make_grid(lo, b + 3, voxel_size, g))
+    return slgpu_fail(c, SL_EINVAL, "voxel grid exceeds 2e6 voxels per axis / 2^63 voxels");
+  return SL_OK;
+}
+
+// The runs of equal keys in a sorted array: flag[i] = 1 at every run's first
+// position, seg = the exclusive scan of flag (a position's run is seg + flag -
+// 1), the run count -> *m.  k_seg_starts turns the pair into the runs' starts.
+int key_runs(sl_ctx* c, const uint64_t* keys, int64_t n, uint32_t* flag, uint32_t* seg, int64_t* m, hipStream_t s) {
+  hipLaunchKernelGGL(k_heads, dim3(blocks(n)), dim3(kT), 0, s, keys, n, flag);
+  return scan_flags(c, flag, n, seg, m, s);
+}
+
+// Orders m index triples (tri [m][3], indices below n_index) by (tri[0] & first_mask, tri[1], tri[2]) with two stable
+// sorts: by the third index, then by the first two as one key.  vals[i] = the triple at rank i; equal triples keep
+// their order.  keys: m entries of scratch.
+int sort_triples(sl_ctx* c, const uint32_t* tri, int64_t m, uint64_t n_index, uint32_t first_mask, uint64_t* keys,
+                 uint32_t* vals, hipStream_t s) {
+  hipLaunchKernelGGL(k_triple_key_c, dim3(blocks(m)), dim3(kT), 0, s, tri, m, keys, vals);
+  MTRY(c, hipGetLastError());
+  int r = radix_sort(c, keys, vals, m, key_bits(n_index - 1), s);
+  if (r) return r;
+  hipLaunchKernelGGL(k_triple_key_ab, dim3(blocks(m)), dim3(kT), 0, s, tri, vals, m, n_index, first_mask, keys);
+  MTRY(c, hipGetLastError());
+  return radix_sort(c, keys, vals, m, key_bits(n_index * n_index - 1), s);
+}
+
 // Sort the points into grid cells: sorted keys + point indices, and the
-// unique cells with their first position.  Returns the cell count in *m.
+// unique cells with their first position.  Returns the cell count in *m.  A
+// caller that goes on to use the sorted keys' head flags and their scan
+// (key_runs) passes a pair of buffers to leave them in.
 int cells(sl_ctx* c, const double* xyz, int64_t n, const Grid& g, DBuf<uint64_t>& keys, DBuf<uint32_t>& idx,
-          DBuf<uint64_t>& ukeys, DBuf<uint32_t>& ustart, int64_t* m, hipStream_t s) {
+          DBuf<uint64_t>& ukeys, DBuf<uint32_t>& ustart, int64_t* m, hipStream_t s,
+          DBuf<uint32_t>* flag_out = nullptr, DBuf<uint32_t>* seg_out = nullptr) {
   MTRY(c, keys.alloc(n));
   MTRY(c, idx.alloc(n));
   hipLaunchKernelGGL(k_cell_keys, dim3(blocks(n)), dim3(kT), 0, s, xyz, n, g.lo0, g.lo1, g.lo2, g.h, g.ny, g.nz,
@@ -1544,11 +1621,12 @@ int cells(sl_ctx* c, const double* xyz, int64_t n, const Grid& g, DBuf<uint64_t>
   const uint64_t max_key = static_cast<uint64_t>((g.nx * g.ny) * g.nz - 1);
   int r = radix_sort(c, keys.p, idx.p, n, key_bits(max_key), s);
   if (r) return r;
-  DBuf<uint32_t> flag, seg;
+  DBuf<uint32_t> own_flag, own_seg;
+  DBuf<uint32_t>& flag = flag_out ? *flag_out : own_flag;
+  DBuf<uint32_t>& seg = seg_out ? *seg_out : own_seg;
   MTRY(c, flag.alloc(n));
   MTRY(c, seg.alloc(n));
-  hipLaunchKernelGGL(k_heads, dim3(blocks(n)), dim3(kT), 0, s, keys.p, n, flag.p);
-  r = scan_flags(c, flag.p, n, seg.p, m, s);
+  r = key_runs(c, keys.p, n, flag.p, seg.p, m, s);
   if (r) return r;
   MTRY(c, ustart.alloc(*m));
   MTRY(c, ukeys.alloc(*m));
@@ -1567,6 +1645,17 @@ int compact_indices(sl_ctx* c, const uint32_t* flag, int64_t n, uint32_t* pos, i
   const int r = scan_flags(c, flag, n, pos, count, s);
   if (r) return r;
   hipLaunchKernelGGL(k_compact_index, dim3(blocks(n)), dim3(kT), 0, s, flag, pos, n, out_index);
+  MTRY(c, hipGetLastError());
+  return SL_OK;
+}
+
+// The same for rows of W values: the flagged rows of in [n][W], in order -> out [*count][W] (room for all of them).
+template <typename T, int W>
+int compact_rows(sl_ctx* c, const T* in, int64_t n, const uint32_t* flag, uint32_t* pos, T* out, int64_t* count,
+                 hipStream_t s) {
+  const int r = scan_flags(c, flag, n, pos, count, s);
+  if (r) return r;
+  hipLaunchKernelGGL((k_compact_rows<T, W>), dim3(blocks(n)), dim3(kT), 0, s, in, n, flag, pos, out);
   MTRY(c, hipGetLastError());
   return SL_OK;
 }
@@ -1642,18 +1731,9 @@ int sl_voxel_downsample(sl_ctx* c, const double* xyz, const uint8_t* bgr, int64_
   double b[6];
   int r = bounds(c, xyz, n, b, s);
   if (r) return r;
-  // voxel_min_bound = min - vs/2, voxel_max_bound = max + vs/2 (VoxelDownSample)
-  double lo[3], hi[3];
-  for (int k = 0; k < 3; ++k) {
-    lo[k] = b[k] - voxel_size * 0.5;
-    hi[k] = b[3 + k] + voxel_size * 0.5;
-  }
-  double ext = 0.0;
-  for (int k = 0; k < 3; ++k) ext = std::max(ext, hi[k] - lo[k]);
-  if (voxel_size * std::numeric_limits<int>::max() < ext) return slgpu_fail(c, SL_EINVAL, "voxel_size is too small.");
   Grid g;
-  if (!make_grid(lo, b + 3, voxel_size, &g))
-    return slgpu_fail(c, SL_EINVAL, "voxel grid exceeds 2e6 voxels per axis / 2^63 voxels");
+  r = voxel_grid(c, b, voxel_size, &g);
+  if (r) return r;
   DBuf<uint64_t> keys, ukeys;
   DBuf<uint32_t> idx, ustart;
   int64_t m = 0;
@@ -2193,11 +2273,14 @@ int sl_merge_pool_poison(int byte, int64_t* poisoned_bytes) {
 
 }  // extern "C"
 
-// global registration (FPFH, feature matching, RANSAC): the same translation unit
+// The feature files, one translation unit with the above.  Each uses this file and slprim.inl (the primitives more
+// than one of them uses) and no other feature file, with one exception: slplane.inl uses slreg.inl's draw.
+#include "slprim.inl"
+// global registration (FPFH, feature matching, RANSAC)
 #include "slreg.inl"
 // plane RANSAC of the per-view background removal (uses slreg.inl's draw)
 #include "slplane.inl"
-
+// Poisson meshing
 #include "slmesh.inl"
 // consistent tangent-plane normal orientation (kNN-graph MST) for the meshing drop-ins
 #include "slorient.inl"

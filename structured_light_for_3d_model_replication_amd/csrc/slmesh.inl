@@ -1,8 +1,9 @@
 // libslgpu.so, part 2d -- Poisson meshing, the fourth step of the reference's
 // workflow (server/processing.py:185-311: create_from_point_cloud_poisson,
 // remove_vertices_by_mask, write_triangle_mesh), included at the end of
-// slmerge.hip (one translation unit: it shares that file's scan kernels and
-// scratch pool and slplane.inl's ordered sum).  Open3D's Poisson is the
+// slmerge.hip (one translation unit: it shares that file's scan and row
+// compaction and scratch pool, and slprim.inl's pieces of the ordered sum that
+// slplane.inl's header defines).  Open3D's Poisson is the
 // adaptive-octree variant and is not in this image; this is Kazhdan's FFT
 // Poisson reconstruction on a dense periodic grid, parity with Open3D is
 // UNPINNED, and tests/mesh_oracle.py is the CPU restatement the tests check
@@ -167,14 +168,14 @@ __global__ __launch_bounds__(kT) void k_mesh_sample(const float* __restrict__ G,
 __global__ __launch_bounds__(kT) void k_osum_part(const double* __restrict__ v, int64_t n, int64_t stride,
                                                   int64_t offset, double* __restrict__ part) {
   __shared__ double s[kT];
-  const int64_t base = static_cast<int64_t>(blockIdx.x) * pln::kChunk + threadIdx.x;
+  const int64_t base = static_cast<int64_t>(blockIdx.x) * prim::kChunk + threadIdx.x;
   double acc = 0.0;
 #pragma unroll 4
-  for (int r = 0; r < pln::kRows; ++r) {
+  for (int r = 0; r < prim::kRows; ++r) {
     const int64_t i = base + static_cast<int64_t>(r) * kT;
     acc = acc + (i < n ? v[stride * i + offset] : 0.0);
   }
-  pln::tree_sum(s, acc);
+  prim::tree_sum(s, acc);
   if (threadIdx.x == 0) part[blockIdx.x] = s[0];
 }
 
@@ -304,12 +305,6 @@ __global__ __launch_bounds__(kT) void k_mesh_emit_t(const float* __restrict__ ch
 }
 
 // remove_vertices_by_mask
-__global__ __launch_bounds__(kT) void k_mesh_keep_v(const uint8_t* __restrict__ mask, int64_t n,
-                                                    uint32_t* __restrict__ keep) {
-  const int64_t i = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
-  if (i < n) keep[i] = mask[i] ? 0u : 1u;
-}
-
 __global__ __launch_bounds__(kT) void k_mesh_keep_t(const int32_t* __restrict__ tris, int64_t n_t, int64_t n_v,
                                                     const uint32_t* __restrict__ keep, uint32_t* __restrict__ tkeep) {
   const int64_t t = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
@@ -321,16 +316,6 @@ __global__ __launch_bounds__(kT) void k_mesh_keep_t(const int32_t* __restrict__ 
     ok &= (v >= 0 && v < n_v) ? keep[v] : 0u;  // (an index outside the mesh drops the triangle; never a load)
   }
   tkeep[t] = ok;
-}
-
-__global__ __launch_bounds__(kT) void k_mesh_gather_v(const double* __restrict__ verts, int64_t n,
-                                                      const uint32_t* __restrict__ keep,
-                                                      const uint32_t* __restrict__ pos, double* __restrict__ out) {
-  const int64_t i = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
-  if (i >= n || !keep[i]) return;
-  const int64_t o = pos[i];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) out[3 * o + a] = verts[3 * i + a];
 }
 
 __global__ __launch_bounds__(kT) void k_mesh_gather_t(const int32_t* __restrict__ tris, int64_t n_t,
@@ -438,12 +423,12 @@ int sl_ordered_sum(sl_ctx* c, const double* v, int64_t n, int64_t stride, int64_
   hipStream_t s = static_cast<hipStream_t>(stream);
   PoolStream pool_stream(s);
   MTRY(c, hipSetDevice(slgpu_device(c)));
-  const int64_t chunks = (n + pln::kChunk - 1) / pln::kChunk;
+  const int64_t chunks = (n + prim::kChunk - 1) / prim::kChunk;
   DBuf<double> part, out;
   MTRY(c, part.alloc(chunks));
   MTRY(c, out.alloc(1));
   hipLaunchKernelGGL(k_osum_part, dim3(static_cast<unsigned>(chunks)), dim3(kT), 0, s, v, n, stride, offset, part.p);
-  hipLaunchKernelGGL(pln::k_plane_fold_sum, dim3(1), dim3(kT), 0, s, part.p, chunks, out.p);
+  hipLaunchKernelGGL(prim::k_plane_fold_sum, dim3(1), dim3(kT), 0, s, part.p, chunks, out.p);
   MTRY(c, hipGetLastError());
   MTRY(c, hipMemcpyAsync(sum, out.p, sizeof(double), hipMemcpyDeviceToHost, s));
   MTRY(c, hipStreamSynchronize(s));
@@ -532,13 +517,10 @@ int sl_mesh_remove_vertices(sl_ctx* c, const double* vertices, int64_t n_vertice
   DBuf<uint32_t> keep, pos, tkeep, tpos;
   MTRY(c, keep.alloc(n_vertices));
   MTRY(c, pos.alloc(n_vertices));
-  hipLaunchKernelGGL(k_mesh_keep_v, dim3(blocks(n_vertices)), dim3(kT), 0, s, mask, n_vertices, keep.p);
+  hipLaunchKernelGGL(k_keep_unmasked, dim3(blocks(n_vertices)), dim3(kT), 0, s, mask, n_vertices, keep.p);
   MTRY(c, hipGetLastError());
-  int r = scan_flags(c, keep.p, n_vertices, pos.p, out_n_vertices, s);
+  int r = compact_rows<double, 3>(c, vertices, n_vertices, keep.p, pos.p, out_vertices, out_n_vertices, s);
   if (r) return r;
-  hipLaunchKernelGGL(k_mesh_gather_v, dim3(blocks(n_vertices)), dim3(kT), 0, s, vertices, n_vertices, keep.p, pos.p,
-                     out_vertices);
-  MTRY(c, hipGetLastError());
   if (n_triangles) {
     MTRY(c, tkeep.alloc(n_triangles));
     MTRY(c, tpos.alloc(n_triangles));

@@ -1,7 +1,7 @@
 // libslgpu.so, part 2i -- mesh clean-up after the density trim, included at the
 // end of slmerge.hip (one translation unit: it shares that file's scratch pool,
-// radix sort, scan, bounds and voxel grid, slcluster.inl's lock-free union-find
-// and slmesh.inl's gather kernel).  Open3D users clean a Poisson mesh with
+// radix and triple sorts, scan, key runs, row compaction, bounds and voxel grid,
+// and slprim.inl's lock-free union-find, input checks and stage clock).  Open3D users clean a Poisson mesh with
 // TriangleMesh::ClusterConnectedTriangles + RemoveTrianglesByMask +
 // RemoveUnreferencedVertices and make it coarser with
 // SimplifyVertexClustering(voxel_size, Average).  They are restated here; Open3D
@@ -59,29 +59,23 @@
 // triangle; radix_sort orders them over the bits V V - 1 has; one thread per
 // sorted position i > 0 with key[i] == key[i-1] unites value[i] and value[i-1]
 // (run neighbours suffice: the chain connects the whole run).  parent[] is
-// indexed by triangle and starts as the identity.  slcluster.inl's argument holds
-// unchanged and is what keeps this wait-free: a root is hooked under a SMALLER
-// root by atomicCAS(parent[a], a, b), b < a, and only roots are hooked, so
-// parents only decrease, no cycle can form, and a component's final root is its
-// smallest triangle index whatever the interleaving; path halving lowers a
-// non-root's parent to an ancestor by atomicMin.  parent words are read by
-// agent-scope relaxed atomic loads; such a read may be stale, and a stale value
-// of parent[x] is x itself or an older ancestor of x, so find_root walks strictly
-// decreasing indices and ends at a point that was a root, and a failed CAS
-// returns the true parent, from which the retry continues strictly lower.  No
-// spin loop, no workgroup waits on another, every loop is bounded by a strictly
-// decreasing index (the wave folds of the counts by a strictly shrinking ballot).
-// After the kernel boundary the trees are walked with plain loads; the root IS
+// indexed by triangle and starts as the identity.  The union-find is slprim.inl's,
+// and the argument in that file's header holds unchanged and is what keeps this
+// wait-free: a component's final root is its smallest triangle index whatever
+// the interleaving, no workgroup waits on another, and every loop is bounded by
+// a strictly decreasing index (the wave folds of the counts by a strictly
+// shrinking ballot).  After the kernel boundary the trees are walked with plain loads; the root IS
 // the smallest index, so the labels are the flag / scan rank of the roots in
 // index order with no min pass.  Counts are integer atomics, one per wave and
 // label.  Areas (only when asked for): a stable sort of the triangles by label,
 // one thread per triangle for A_t, one per 64-block, one per cluster.
 //
 // Simplification on the device.  cells() sorts the vertices by voxel key (stable:
-// a run's first entry is its smallest index); the heads' flags at their vertex
-// index are scanned for the first-encounter rank; one thread per voxel averages.
-// The mapped, rotated triangles that survive are compacted in input order, then
-// sorted twice (stable, value = compacted position): by c, then by a V' + b (up
+// a run's first entry is its smallest index) and leaves the sorted keys' head
+// flags and their scan; the heads' flags at their vertex index are scanned for
+// the first-encounter rank; one thread per voxel averages.  The mapped, rotated
+// triangles that survive are compacted in input order, then sorted by
+// sort_triples (stable, value = compacted position: by c, then by a V' + b, up
 // to 93 key bits in all); a run head is flagged at its compacted position, the
 // flags are scanned and the heads gathered: input order of first occurrences.
 
@@ -92,12 +86,7 @@ constexpr int kBlock = 64;  // members per area block
 
 thread_local double tls_ms[6];  // edge keys, sort, union, flatten + rank, counts, areas of the last clustering
 
-__global__ __launch_bounds__(kT) void k_mc_check(const int32_t* tris, int64_t n3, int64_t n_v, unsigned* bad) {
-  const int64_t i = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
-  if (i >= n3) return;
-  const int64_t v = tris[i];
-  if (v < 0 || v >= n_v) atomicOr(bad, 1u);
-}
+using prim::require_finite, prim::require_indices;  // the latter: k_mc_check
 
 __global__ __launch_bounds__(kT) void k_mc_edges(const int32_t* tris, int64_t n_t, uint64_t n_v, uint64_t* keys,
                                                  uint32_t* vals) {
@@ -116,7 +105,7 @@ __global__ __launch_bounds__(kT) void k_mc_union(const uint64_t* keys, const uin
   const int64_t i = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
   if (i < 1 || i >= n3 || keys[i] != keys[i - 1]) return;
   const uint32_t a = vals[i], b = vals[i - 1];
-  if (a != b) clu::unite(parent, a, b);
+  if (a != b) prim::unite(parent, a, b);
 }
 
 // After the unions (a kernel boundary: plain loads): root[t], and flag[t] = 1 for the roots.
@@ -215,21 +204,7 @@ __global__ __launch_bounds__(kT) void k_mc_cluster_fold(const double* bsum, cons
   out[c] = s;
 }
 
-// ---- masks
-__global__ __launch_bounds__(kT) void k_mc_keep(const uint8_t* mask, int64_t n, uint32_t* keep) {
-  const int64_t i = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
-  if (i < n) keep[i] = mask[i] ? 0u : 1u;
-}
-
-__global__ __launch_bounds__(kT) void k_mc_gather3(const int32_t* tris, int64_t n, const uint32_t* keep,
-                                                   const uint32_t* pos, int32_t* out) {
-  const int64_t t = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
-  if (t >= n || !keep[t]) return;
-  const int64_t o = pos[t];
-#pragma unroll
-  for (int s = 0; s < 3; ++s) out[3 * o + s] = tris[3 * t + s];
-}
-
+// ---- unreferenced vertices
 // ref[v] = 1 for every referenced vertex (the same word from every writer; indices were checked)
 __global__ __launch_bounds__(kT) void k_mc_mark(const int32_t* tris, int64_t n3, uint32_t* ref) {
   const int64_t i = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
@@ -299,32 +274,6 @@ __global__ __launch_bounds__(kT) void k_sc_tris(const int32_t* tris, int64_t n_t
   ok[t] = (a != b && b != c && c != a) ? 1u : 0u;
 }
 
-__global__ __launch_bounds__(kT) void k_sc_compact(const uint32_t* rot, int64_t n_t, const uint32_t* ok,
-                                                   const uint32_t* pos, uint32_t* out) {
-  const int64_t t = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
-  if (t >= n_t || !ok[t]) return;
-  const int64_t o = pos[t];
-#pragma unroll
-  for (int s = 0; s < 3; ++s) out[3 * o + s] = rot[3 * t + s];
-}
-
-// first sort: by c, value = the compacted position
-__global__ __launch_bounds__(kT) void k_sc_key_c(const uint32_t* tri, int64_t n, uint64_t* keys, uint32_t* vals) {
-  const int64_t j = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
-  if (j >= n) return;
-  keys[j] = tri[3 * j + 2];
-  vals[j] = static_cast<uint32_t>(j);
-}
-
-// second sort: by a V' + b of the triangles in the first sort's order
-__global__ __launch_bounds__(kT) void k_sc_key_ab(const uint32_t* tri, const uint32_t* vals, int64_t n, uint64_t n_v,
-                                                  uint64_t* keys) {
-  const int64_t i = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
-  if (i >= n) return;
-  const int64_t j = vals[i];
-  keys[i] = static_cast<uint64_t>(tri[3 * j]) * n_v + tri[3 * j + 1];
-}
-
 // head[j] = 1 for the first occurrence (the smallest compacted position: the sorts are stable) of every triple
 __global__ __launch_bounds__(kT) void k_sc_heads(const uint32_t* tri, const uint32_t* vals, int64_t n, uint32_t* head) {
   const int64_t i = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
@@ -336,29 +285,6 @@ __global__ __launch_bounds__(kT) void k_sc_heads(const uint32_t* tri, const uint
     first = tri[3 * j] != tri[3 * q] || tri[3 * j + 1] != tri[3 * q + 1] || tri[3 * j + 2] != tri[3 * q + 2];
   }
   head[j] = first ? 1u : 0u;
-}
-
-__global__ __launch_bounds__(kT) void k_sc_emit(const uint32_t* tri, int64_t n, const uint32_t* head,
-                                                const uint32_t* pos, int32_t* out) {
-  const int64_t j = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
-  if (j >= n || !head[j]) return;
-  const int64_t o = pos[j];
-#pragma unroll
-  for (int s = 0; s < 3; ++s) out[3 * o + s] = static_cast<int32_t>(tri[3 * j + s]);
-}
-
-// SL_EINDEX with `msg` when an index is outside 0 .. n_v - 1 (nothing is indexed here).
-int require_indices(sl_ctx* c, const int32_t* tris, int64_t n_t, int64_t n_v, const char* msg, hipStream_t s) {
-  if (n_t == 0) return SL_OK;
-  DBuf<unsigned> bad;
-  MTRY(c, bad.alloc(1));
-  MTRY(c, hipMemsetAsync(bad.p, 0, sizeof(unsigned), s));
-  hipLaunchKernelGGL(k_mc_check, dim3(blocks(3 * n_t)), dim3(kT), 0, s, tris, 3 * n_t, n_v, bad.p);
-  MTRY(c, hipGetLastError());
-  unsigned h = 0;
-  MTRY(c, hipMemcpyAsync(&h, bad.p, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-  MTRY(c, hipStreamSynchronize(s));
-  return h ? slgpu_fail(c, SL_EINDEX, msg) : SL_OK;
 }
 
 bool bad_sizes(int64_t n_v, int64_t n_t) {
@@ -388,10 +314,10 @@ int sl_mesh_cluster_triangles(sl_ctx* c, const double* vertices, int64_t n_verti
   int r = require_indices(c, triangles, n, n_vertices, "sl_mesh_cluster_triangles: triangle index out of range", s);
   if (r) return r;
   if (cluster_area) {
-    r = clu::require_finite(c, vertices, n_vertices, "sl_mesh_cluster_triangles: non-finite vertex coordinates", s);
+    r = require_finite(c, vertices, n_vertices, "sl_mesh_cluster_triangles: non-finite vertex coordinates", s);
     if (r) return r;
   }
-  clu::StageClock clock(s);
+  prim::StageClock clock(s);
   const uint64_t nv = static_cast<uint64_t>(n_vertices);
   DBuf<uint32_t> parent, root, flag, pos;
   MTRY(c, parent.alloc(n));
@@ -401,7 +327,7 @@ int sl_mesh_cluster_triangles(sl_ctx* c, const double* vertices, int64_t n_verti
     MTRY(c, keys.alloc(n3));
     MTRY(c, vals.alloc(n3));
     hipLaunchKernelGGL(k_mc_edges, dim3(blocks(n)), dim3(kT), 0, s, triangles, n, nv, keys.p, vals.p);
-    hipLaunchKernelGGL(clu::k_clu_init, dim3(blocks(n)), dim3(kT), 0, s, n, parent.p);
+    hipLaunchKernelGGL(prim::k_clu_init, dim3(blocks(n)), dim3(kT), 0, s, n, parent.p);
     MTRY(c, hipGetLastError());
     MTRY(c, clock.lap(&tls_ms[0]));
     r = radix_sort(c, keys.p, vals.p, n3, key_bits(nv * nv - 1), s);  // only the bits the keys have
@@ -441,10 +367,8 @@ int sl_mesh_cluster_triangles(sl_ctx* c, const double* vertices, int64_t n_verti
     MTRY(c, seg.alloc(n));
     MTRY(c, starts.alloc(clusters));
     MTRY(c, ukeys.alloc(clusters));
-    hipLaunchKernelGGL(k_heads, dim3(blocks(n)), dim3(kT), 0, s, keys.p, n, flag.p);
-    MTRY(c, hipGetLastError());
     int64_t runs = 0;
-    r = scan_flags(c, flag.p, n, seg.p, &runs, s);
+    r = key_runs(c, keys.p, n, flag.p, seg.p, &runs, s);
     if (r) return r;
     if (runs != clusters) return slgpu_fail(c, SL_EHIP, "sl_mesh_cluster_triangles: label runs and clusters differ");
     hipLaunchKernelGGL(k_seg_starts, dim3(blocks(n)), dim3(kT), 0, s, flag.p, seg.p, keys.p, n, starts.p, ukeys.p);
@@ -491,12 +415,10 @@ int sl_mesh_remove_triangles(sl_ctx* c, const int32_t* triangles, int64_t n_tria
   DBuf<uint32_t> keep, pos;
   MTRY(c, keep.alloc(n));
   MTRY(c, pos.alloc(n));
-  hipLaunchKernelGGL(k_mc_keep, dim3(blocks(n)), dim3(kT), 0, s, mask, n, keep.p);
+  hipLaunchKernelGGL(k_keep_unmasked, dim3(blocks(n)), dim3(kT), 0, s, mask, n, keep.p);
   MTRY(c, hipGetLastError());
-  int r = scan_flags(c, keep.p, n, pos.p, out_n_triangles, s);
+  int r = compact_rows<int32_t, 3>(c, triangles, n, keep.p, pos.p, out_triangles, out_n_triangles, s);
   if (r) return r;
-  hipLaunchKernelGGL(k_mc_gather3, dim3(blocks(n)), dim3(kT), 0, s, triangles, n, keep.p, pos.p, out_triangles);
-  MTRY(c, hipGetLastError());
   MTRY(c, hipStreamSynchronize(s));
   return SL_OK;
 }
@@ -524,10 +446,8 @@ int sl_mesh_remove_unreferenced(sl_ctx* c, const double* vertices, int64_t n_ver
   MTRY(c, hipMemsetAsync(ref.p, 0, sizeof(uint32_t) * n_vertices, s));
   if (n3) hipLaunchKernelGGL(k_mc_mark, dim3(blocks(n3)), dim3(kT), 0, s, triangles, n3, ref.p);
   MTRY(c, hipGetLastError());
-  r = scan_flags(c, ref.p, n_vertices, pos.p, out_n_vertices, s);
+  r = compact_rows<double, 3>(c, vertices, n_vertices, ref.p, pos.p, out_vertices, out_n_vertices, s);
   if (r) return r;
-  hipLaunchKernelGGL(msh::k_mesh_gather_v, dim3(blocks(n_vertices)), dim3(kT), 0, s, vertices, n_vertices, ref.p, pos.p,
-                     out_vertices);
   if (n3) hipLaunchKernelGGL(k_mc_remap, dim3(blocks(n3)), dim3(kT), 0, s, triangles, n3, pos.p, out_triangles);
   MTRY(c, hipGetLastError());
   MTRY(c, hipStreamSynchronize(s));
@@ -551,40 +471,25 @@ int sl_mesh_simplify_clustering(sl_ctx* c, const double* vertices, int64_t n_ver
   int r = require_indices(c, triangles, nt, n, "sl_mesh_simplify_clustering: triangle index out of range", s);
   if (r) return r;
   if (n == 0) return SL_OK;
-  r = clu::require_finite(c, vertices, n, "sl_mesh_simplify_clustering: non-finite vertex coordinates", s);
+  r = require_finite(c, vertices, n, "sl_mesh_simplify_clustering: non-finite vertex coordinates", s);
   if (r) return r;
   double b[6];
   r = bounds(c, vertices, n, b, s);
   if (r) return r;
-  // sl_voxel_downsample's grid: voxel_min_bound = min - vs/2, voxel_max_bound = max + vs/2
-  double lo[3], hi[3];
-  for (int k = 0; k < 3; ++k) {
-    lo[k] = b[k] - voxel_size * 0.5;
-    hi[k] = b[3 + k] + voxel_size * 0.5;
-  }
-  double ext = 0.0;
-  for (int k = 0; k < 3; ++k) ext = std::max(ext, hi[k] - lo[k]);
-  if (voxel_size * std::numeric_limits<int>::max() < ext) return slgpu_fail(c, SL_EINVAL, "voxel_size is too small.");
-  Grid g;
-  if (!make_grid(lo, b + 3, voxel_size, &g))
-    return slgpu_fail(c, SL_EINVAL, "voxel grid exceeds 2e6 voxels per axis / 2^63 voxels");
+  Grid g;  // sl_voxel_downsample's
+  r = voxel_grid(c, b, voxel_size, &g);
+  if (r) return r;
   DBuf<uint32_t> vmap;
   MTRY(c, vmap.alloc(n));
   int64_t m = 0;
   {
     DBuf<uint64_t> keys, ukeys;
-    DBuf<uint32_t> idx, ustart, flag, seg, first, rank;
-    r = cells(c, vertices, n, g, keys, idx, ukeys, ustart, &m, s);
+    DBuf<uint32_t> idx, ustart, flag, seg, first, rank;  // flag, seg: the sorted keys' run heads and their scan
+    r = cells(c, vertices, n, g, keys, idx, ukeys, ustart, &m, s, &flag, &seg);
     if (r) return r;
-    MTRY(c, flag.alloc(n));
-    MTRY(c, seg.alloc(n));
     MTRY(c, first.alloc(n));
     MTRY(c, rank.alloc(n));
-    hipLaunchKernelGGL(k_heads, dim3(blocks(n)), dim3(kT), 0, s, keys.p, n, flag.p);
-    MTRY(c, hipGetLastError());
     int64_t runs = 0;
-    r = scan_flags(c, flag.p, n, seg.p, &runs, s);
-    if (r) return r;
     MTRY(c, hipMemsetAsync(first.p, 0, sizeof(uint32_t) * n, s));
     hipLaunchKernelGGL(k_sc_first, dim3(blocks(m)), dim3(kT), 0, s, ustart.p, idx.p, m, first.p);
     MTRY(c, hipGetLastError());
@@ -610,7 +515,7 @@ int sl_mesh_simplify_clustering(sl_ctx* c, const double* vertices, int64_t n_ver
   if (r) return r;
   if (live == 0) return SL_OK;
   MTRY(c, tri.alloc(3 * live));
-  hipLaunchKernelGGL(k_sc_compact, dim3(blocks(nt)), dim3(kT), 0, s, rot.p, nt, ok.p, pos.p, tri.p);
+  hipLaunchKernelGGL((k_compact_rows<uint32_t, 3>), dim3(blocks(nt)), dim3(kT), 0, s, rot.p, nt, ok.p, pos.p, tri.p);
   MTRY(c, hipGetLastError());
   DBuf<uint64_t> keys;
   DBuf<uint32_t> vals, head, hpos;
@@ -618,21 +523,14 @@ int sl_mesh_simplify_clustering(sl_ctx* c, const double* vertices, int64_t n_ver
   MTRY(c, vals.alloc(live));
   MTRY(c, head.alloc(live));
   MTRY(c, hpos.alloc(live));
-  const uint64_t mv = static_cast<uint64_t>(m);
-  hipLaunchKernelGGL(k_sc_key_c, dim3(blocks(live)), dim3(kT), 0, s, tri.p, live, keys.p, vals.p);
-  MTRY(c, hipGetLastError());
-  r = radix_sort(c, keys.p, vals.p, live, key_bits(mv - 1), s);
-  if (r) return r;
-  hipLaunchKernelGGL(k_sc_key_ab, dim3(blocks(live)), dim3(kT), 0, s, tri.p, vals.p, live, mv, keys.p);
-  MTRY(c, hipGetLastError());
-  r = radix_sort(c, keys.p, vals.p, live, key_bits(mv * mv - 1), s);
+  r = sort_triples(c, tri.p, live, static_cast<uint64_t>(m), 0xffffffffu, keys.p, vals.p, s);
   if (r) return r;
   hipLaunchKernelGGL(k_sc_heads, dim3(blocks(live)), dim3(kT), 0, s, tri.p, vals.p, live, head.p);
   MTRY(c, hipGetLastError());
-  r = scan_flags(c, head.p, live, hpos.p, out_n_triangles, s);
+  // the first occurrences in input order (the indices are below 2^31: the same bits as int32)
+  r = compact_rows<uint32_t, 3>(c, tri.p, live, head.p, hpos.p, reinterpret_cast<uint32_t*>(out_triangles),
+                                out_n_triangles, s);
   if (r) return r;
-  hipLaunchKernelGGL(k_sc_emit, dim3(blocks(live)), dim3(kT), 0, s, tri.p, live, head.p, hpos.p, out_triangles);
-  MTRY(c, hipGetLastError());
   MTRY(c, hipStreamSynchronize(s));
   return SL_OK;
 }

@@ -1,6 +1,6 @@
 // libslgpu.so, part 2j -- writing a triangle mesh from device memory, included at
 // the end of slmerge.hip (one translation unit: it shares that file's scratch
-// pool and slmeshclean.inl's index check).  o3d.io.write_triangle_mesh for
+// pool and slprim.inl's index check).  o3d.io.write_triangle_mesh for
 // ``.stl`` and ``.ply`` after compute_vertex_normals(): the records are packed
 // on the device and streamed to the file through a small ring of pinned chunks.
 // Open3D is not in this image, so its PLY layout and its NormalizeNormals rule
@@ -433,7 +433,7 @@ int sl_mesh_triangle_normals(sl_ctx* c, const double* vertices, int64_t n_vertic
   hipStream_t s = static_cast<hipStream_t>(stream);
   PoolStream pool_stream(s);
   MTRY(c, hipSetDevice(slgpu_device(c)));
-  int r = mcl::require_indices(c, triangles, n_triangles, n_vertices,
+  int r = prim::require_indices(c, triangles, n_triangles, n_vertices,
                                "sl_mesh_triangle_normals: triangle index out of range", s);
   if (r) return r;
   hipLaunchKernelGGL(k_mw_tri_normals, dim3(blocks(n_triangles)), dim3(kT), 0, s, vertices, triangles, n_triangles,
@@ -452,7 +452,7 @@ int sl_mesh_vertex_normals(sl_ctx* c, const double* vertices, int64_t n_vertices
   hipStream_t s = static_cast<hipStream_t>(stream);
   PoolStream pool_stream(s);
   MTRY(c, hipSetDevice(slgpu_device(c)));
-  int r = mcl::require_indices(c, triangles, n_triangles, n_vertices,
+  int r = prim::require_indices(c, triangles, n_triangles, n_vertices,
                                "sl_mesh_vertex_normals: triangle index out of range", s);
   if (r) return r;
   if (n_vertices == 0) return SL_OK;
@@ -477,7 +477,7 @@ int sl_write_stl_device(sl_ctx* c, const char* path, const double* vertices, int
   hipStream_t s = static_cast<hipStream_t>(stream);
   PoolStream pool_stream(s);
   MTRY(c, hipSetDevice(slgpu_device(c)));
-  int r = mcl::require_indices(c, triangles, n_triangles, n_vertices, "sl_write_stl_device: triangle index out of range",
+  int r = prim::require_indices(c, triangles, n_triangles, n_vertices, "sl_write_stl_device: triangle index out of range",
                                s);
   if (r) return r;
   Ring* ring = nullptr;
@@ -508,7 +508,7 @@ int sl_write_mesh_ply_device(sl_ctx* c, const char* path, const double* vertices
   hipStream_t s = static_cast<hipStream_t>(stream);
   PoolStream pool_stream(s);
   MTRY(c, hipSetDevice(slgpu_device(c)));
-  int r = mcl::require_indices(c, triangles, n_triangles, n_vertices,
+  int r = prim::require_indices(c, triangles, n_triangles, n_vertices,
                                "sl_write_mesh_ply_device: triangle index out of range", s);
   if (r) return r;
   Ring* ring = nullptr;

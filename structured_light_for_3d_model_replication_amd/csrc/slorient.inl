@@ -1,6 +1,6 @@
 // libslgpu.so, part 2e -- consistent tangent-plane normal orientation, included
 // at the end of slmerge.hip (one translation unit: it shares that file's scratch
-// pool and scan).  The reference calls Open3D's orient_normals_consistent_
+// pool, scan and row compaction and slprim.inl's fold_min).  The reference calls Open3D's orient_normals_consistent_
 // tangent_plane(100) (server/processing.py:201, :282): a minimum spanning tree
 // of a Riemannian graph (Delaunay-EMST edges plus kNN edges, weight 1 - |ni.nj|)
 // walked from the highest point.  This is a restatement on the kNN graph ALONE
@@ -66,7 +66,8 @@ namespace ort {
 constexpr uint32_t kNone = 0xffffffffu;
 constexpr unsigned long long kNoEdge = ~0ull;
 constexpr unsigned long long kFlipBit = 1ull << 63;
-constexpr int kFold = 4;  // labels a wave folds before its remaining lanes go alone
+
+using prim::fold_min;  // one atomicMin per wave and label
 
 struct Stats {
   int rounds = 0;
@@ -89,30 +90,6 @@ __device__ __forceinline__ unsigned long long weight_bits(double dot) {
 __device__ __forceinline__ unsigned long long z_bits(double z) {
   const unsigned long long b = static_cast<unsigned long long>(__double_as_longlong(z + 0.0));
   return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-
-// atomicMin(dst[label], key) of every pending lane.  Called by all lanes of the
-// wave together (no lane has returned); lanes that share the first pending lane's
-// label fold into one atomic, kFold times, then every lane left goes alone.
-template <typename T>
-__device__ __forceinline__ void fold_min(T* dst, uint32_t label, T key, bool pending) {
-  const int lane = threadIdx.x & 63;
-  for (int it = 0; it < kFold; ++it) {
-    const unsigned long long m = __ballot(pending);
-    if (!m) return;  // wave-uniform
-    const int leader = __ffsll(m) - 1;
-    const uint32_t L = __shfl(label, leader);
-    const bool mine = pending && label == L;
-    T v = mine ? key : static_cast<T>(~static_cast<T>(0));
-#pragma unroll
-    for (int o = 32; o; o >>= 1) {
-      const T t = __shfl_xor(v, o);
-      v = t < v ? t : v;
-    }
-    if (lane == leader) atomicMin(dst + L, v);
-    pending = pending && !mine;
-  }
-  if (pending) atomicMin(dst + label, key);
 }
 
 __global__ __launch_bounds__(kT) void k_ort_init(int64_t n, uint32_t* word, uint8_t* alive, uint32_t* tslot) {
@@ -267,13 +244,6 @@ __global__ __launch_bounds__(kT) void k_ort_tree_flag(const uint32_t* __restrict
   if (v < n) flag[v] = tslot[v] != kNone ? 1u : 0u;
 }
 
-__global__ __launch_bounds__(kT) void k_ort_tree_emit(const uint32_t* __restrict__ tslot, int64_t n,
-                                                      const uint32_t* __restrict__ pos, int64_t n_tree,
-                                                      uint32_t* __restrict__ out) {
-  const int64_t v = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
-  if (v < n && tslot[v] != kNone && pos[v] < n_tree) out[pos[v]] = tslot[v];
-}
-
 int read_u32(sl_ctx* c, const unsigned* dev, unsigned* host, hipStream_t s) {
   MTRY(c, hipMemcpyAsync(host, dev, sizeof(unsigned), hipMemcpyDeviceToHost, s));
   MTRY(c, hipStreamSynchronize(s));
@@ -389,7 +359,8 @@ int sl_orient_normals_mst(sl_ctx* c, const double* xyz, double* normals, int64_t
     if (r) return r;
     if (t != hooked)
       return slgpu_fail(c, SL_EHIP, "sl_orient_normals_mst: internal error: the tree list is incomplete");
-    hipLaunchKernelGGL(k_ort_tree_emit, dim3(gv), dim3(kT), 0, s, tslot.p, n, cs.p, hooked, tree_slots);
+    // (the scan's total is `hooked`, so every flagged row's position is below it: tree_slots' size)
+    hipLaunchKernelGGL((k_compact_rows<uint32_t, 1>), dim3(gv), dim3(kT), 0, s, tslot.p, n, next, cs.p, tree_slots);
     MTRY(c, hipGetLastError());
     MTRY(c, hipStreamSynchronize(s));
   }

@@ -1,8 +1,9 @@
 // libslgpu.so, part 2c -- background removal of the per-view clean-up
 // (server/processing.py:25-52, page 2 of the reference GUI): Open3D's
 // PointCloud::SegmentPlane, included at the end of slmerge.hip (one translation
-// unit: it shares that file's scan / compact kernels and scratch pool, and
-// slreg.inl's draw).  Open3D is not in this image: the algorithm is restated
+// unit: it shares that file's scan / compact kernels and scratch pool,
+// slreg.inl's draw, and slprim.inl's chunk shape, tree and fold kernel of the
+// ordered sum defined below).  Open3D is not in this image: the algorithm is restated
 // from its published source (geometry/PointCloudSegmentation.cpp), parity with
 // Open3D is UNPINNED, and tests/plane_oracle.py is the CPU restatement the
 // tests check against bit for bit.  All arithmetic is f64, uncontracted, in
@@ -50,8 +51,7 @@
 namespace {
 namespace pln {
 
-constexpr int kRows = 16;             // rows of a chunk each lane holds
-constexpr int kChunk = kT * kRows;    // 4096 points
+using prim::kChunk, prim::kRows, prim::tree_sum, prim::k_plane_fold_sum;  // the ordered sum's shared pieces
 constexpr int kMaxH = 256;            // planes per scoring launch
 constexpr int kMaxBatch = 4096;       // hypotheses per host round trip
 constexpr int kMaxRn = 16;
@@ -172,18 +172,6 @@ __device__ __forceinline__ void load_chunk(const double* __restrict__ xyz, int64
   }
 }
 
-// The tree of the ordered sum over the workgroup's 256 lane sums -> s[0].
-__device__ __forceinline__ void tree_sum(double* s, double v) {
-  const int t = threadIdx.x;
-  s[t] = v;
-  __syncthreads();
-#pragma unroll
-  for (int w = kT / 2; w > 0; w >>= 1) {
-    if (t < w) s[t] = s[t] + s[t + w];
-    __syncthreads();
-  }
-}
-
 // The hot pass: one workgroup streams its chunk once and counts its inliers
 // under each of the batch's H (<= kMaxH) planes -> part[h][chunk].  The plane
 // is wave-uniform (scalar loads); a row's inliers are one ballot's popcount.
@@ -251,24 +239,6 @@ __global__ __launch_bounds__(kT) void k_plane_err(const double* __restrict__ xyz
     if (threadIdx.x == 0) part[static_cast<int64_t>(h) * chunks + blockIdx.x] = s[0];
     __syncthreads();
   }
-}
-
-// row blockIdx.x of part[rows][chunks]: the chunk sums added to 0.0 left to right
-__global__ __launch_bounds__(kT) void k_plane_fold_sum(const double* __restrict__ part, int64_t chunks,
-                                                       double* __restrict__ out) {
-  __shared__ double s[kT];
-  const double* row = part + static_cast<int64_t>(blockIdx.x) * chunks;
-  double acc = 0.0;
-  for (int64_t c0 = 0; c0 < chunks; c0 += kT) {
-    if (c0 + threadIdx.x < chunks) s[threadIdx.x] = row[c0 + threadIdx.x];
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const int m = static_cast<int>(min<int64_t>(kT, chunks - c0));
-      for (int j = 0; j < m; ++j) acc = acc + s[j];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[blockIdx.x] = acc;
 }
 
 // inlier flags under the best plane, and their complement

@@ -1,0 +1,206 @@
+// libslgpu.so, part 2a -- the primitives the feature files share, included at
+// the end of slmerge.hip before the first of them (one translation unit: it uses
+// that file's scratch pool and launch helpers).  What belongs here: a small
+// device or host piece that MORE THAN ONE feature file uses.  Nothing here is an
+// algorithm of its own or names a feature's namespace; a feature file names
+// slmerge.hip proper and prim::, never another feature (DESIGN.md, Appendix C.1
+// lists every piece's users).  Kernels keep the names they had where they came
+// from: profiles and the benches' kernel groups know them by those.
+//
+// Lock-free union-find: why it is wait-free (the one statement of the argument).
+// parent[] starts as the identity (k_clu_init).  A root is hooked under a SMALLER
+// root by atomicCAS(parent[a], a, b), b < a, and only roots are hooked, so
+// parents only decrease, no cycle can form, and a component's final root is its
+// smallest member whatever the interleaving.  Path halving lowers a non-root's
+// parent to an ancestor by atomicMin.
+// Stale reads.  Within a launch the L1s and the per-XCD L2s are not coherent;
+// parent words are read by agent-scope relaxed atomic loads, and even those may
+// return an older value.  An older value of parent[x] is x itself or an older
+// ancestor of x (a word only ever moves down its own ancestor chain), so:
+//   - find_root() walks strictly decreasing indices and ends at a point that WAS
+//     a root: no wait, no spin;
+//   - a hook on a point that is no longer a root fails its CAS, which returns
+//     the true parent, and the loop continues from THAT value (never from a
+//     plain re-read), so every retry is strictly lower: progress without
+//     waiting on another workgroup;
+//   - "both ends share an ancestor" is true of stale ancestors only if it is
+//     true: ancestors are never un-made.
+// A stale read therefore costs steps and never a wrong union; the atomics
+// themselves act on the one copy at the device's coherence point.  After the
+// launch (a kernel boundary makes everything visible) the trees are walked with
+// plain loads.
+//
+// Ordered sum: slplane.inl's header DEFINES the summation order (chunks of
+// kChunk points, kRows rows a lane, tree_sum, the chunk sums left to right);
+// the pieces of it that slmesh.inl's sl_ordered_sum needs as well live here.
+
+#include <time.h>
+
+namespace {
+namespace prim {
+
+// ---------------------------------------------------------------- fold_min ----
+constexpr int kFold = 4;  // labels a wave folds before its remaining lanes go alone
+
+// atomicMin(dst[label], key) of every pending lane.  Called by all lanes of the
+// wave together (no lane has returned); lanes that share the first pending lane's
+// label fold into one atomic, kFold times, then every lane left goes alone.
+template <typename T>
+__device__ __forceinline__ void fold_min(T* dst, uint32_t label, T key, bool pending) {
+  const int lane = threadIdx.x & 63;
+  for (int it = 0; it < kFold; ++it) {
+    const unsigned long long m = __ballot(pending);
+    if (!m) return;  // wave-uniform
+    const int leader = __ffsll(m) - 1;
+    const uint32_t L = __shfl(label, leader);
+    const bool mine = pending && label == L;
+    T v = mine ? key : static_cast<T>(~static_cast<T>(0));
+#pragma unroll
+    for (int o = 32; o; o >>= 1) {
+      const T t = __shfl_xor(v, o);
+      v = t < v ? t : v;
+    }
+    if (lane == leader) atomicMin(dst + L, v);
+    pending = pending && !mine;
+  }
+  if (pending) atomicMin(dst + label, key);
+}
+
+// -------------------------------------------------------------- union-find ----
+__device__ __forceinline__ uint32_t ld_parent(const uint32_t* p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// A point that is (or, read stale, was) the root of x's tree; halves the path.
+__device__ __forceinline__ uint32_t find_root(uint32_t* parent, uint32_t x) {
+  for (;;) {
+    const uint32_t p = ld_parent(parent + x);
+    if (p == x) return x;
+    const uint32_t g = ld_parent(parent + p);
+    if (g == p) return p;
+    atomicMin(parent + x, g);  // g <= p < x: an ancestor of x
+    x = g;
+  }
+}
+
+// One tree for a and b; returns a point that is an ancestor of both.
+__device__ __forceinline__ uint32_t unite(uint32_t* parent, uint32_t a, uint32_t b) {
+  for (;;) {
+    a = find_root(parent, a);
+    b = find_root(parent, b);
+    if (a == b) return a;
+    if (a < b) {
+      const uint32_t t = a;
+      a = b;
+      b = t;
+    }
+    const uint32_t old = atomicCAS(parent + a, a, b);  // the larger root under the smaller
+    if (old == a) return b;
+    a = old;  // a had been hooked already: go on from its true parent (< a)
+  }
+}
+
+__global__ __launch_bounds__(kT) void k_clu_init(int64_t n, uint32_t* parent) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
+  if (i < n) parent[i] = static_cast<uint32_t>(i);
+}
+
+// -------------------------------------------------------------- StageClock ----
+// Host milliseconds of a stage, read once the stream is idle.
+struct StageClock {
+  hipStream_t s;
+  double t0;
+  static double now() {
+    timespec ts;
+    clock_gettime(CLOCK_MONOTONIC, &ts);
+    return 1e3 * static_cast<double>(ts.tv_sec) + 1e-6 * static_cast<double>(ts.tv_nsec);
+  }
+  explicit StageClock(hipStream_t st) : s(st), t0(now()) {}
+  hipError_t lap(double* ms) {
+    const hipError_t e = hipStreamSynchronize(s);
+    const double t = now();
+    *ms = t - t0;
+    t0 = t;
+    return e;
+  }
+};
+
+// ---------------------------------------------------------- input checks ----
+// Zero one word, let `launch(word)` queue a kernel that raises it on a bad
+// input, read it back: `code` with the caller's `msg` when it was raised.
+template <typename Launch>
+int require_clear(sl_ctx* c, int code, const char* msg, hipStream_t s, Launch launch) {
+  DBuf<unsigned> bad;
+  MTRY(c, bad.alloc(1));
+  MTRY(c, hipMemsetAsync(bad.p, 0, sizeof(unsigned), s));
+  launch(bad.p);
+  MTRY(c, hipGetLastError());
+  unsigned h = 0;
+  MTRY(c, hipMemcpyAsync(&h, bad.p, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+  MTRY(c, hipStreamSynchronize(s));
+  return h ? slgpu_fail(c, code, msg) : SL_OK;
+}
+
+__global__ __launch_bounds__(kT) void k_clu_finite(const double* xyz, int64_t n3, unsigned* bad) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
+  if (i < n3 && !isfinite(xyz[i])) atomicOr(bad, 1u);
+}
+
+// SL_EINVAL with `msg` when a coordinate is not finite.
+int require_finite(sl_ctx* c, const double* xyz, int64_t n, const char* msg, hipStream_t s) {
+  return require_clear(c, SL_EINVAL, msg, s, [&](unsigned* bad) {
+    hipLaunchKernelGGL(k_clu_finite, dim3(blocks(3 * n)), dim3(kT), 0, s, xyz, 3 * n, bad);
+  });
+}
+
+__global__ __launch_bounds__(kT) void k_mc_check(const int32_t* tris, int64_t n3, int64_t n_v, unsigned* bad) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
+  if (i >= n3) return;
+  const int64_t v = tris[i];
+  if (v < 0 || v >= n_v) atomicOr(bad, 1u);
+}
+
+// SL_EINDEX with `msg` when an index is outside 0 .. n_v - 1 (nothing is indexed here).
+int require_indices(sl_ctx* c, const int32_t* tris, int64_t n_t, int64_t n_v, const char* msg, hipStream_t s) {
+  if (n_t == 0) return SL_OK;
+  return require_clear(c, SL_EINDEX, msg, s, [&](unsigned* bad) {
+    hipLaunchKernelGGL(k_mc_check, dim3(blocks(3 * n_t)), dim3(kT), 0, s, tris, 3 * n_t, n_v, bad);
+  });
+}
+
+// ------------------------------------------------------------- ordered sum ----
+constexpr int kRows = 16;           // rows of a chunk each lane holds
+constexpr int kChunk = kT * kRows;  // 4096 points
+
+// The tree of the ordered sum over the workgroup's 256 lane sums -> s[0].
+__device__ __forceinline__ void tree_sum(double* s, double v) {
+  const int t = threadIdx.x;
+  s[t] = v;
+  __syncthreads();
+#pragma unroll
+  for (int w = kT / 2; w > 0; w >>= 1) {
+    if (t < w) s[t] = s[t] + s[t + w];
+    __syncthreads();
+  }
+}
+
+// row blockIdx.x of part[rows][chunks]: the chunk sums added to 0.0 left to right
+__global__ __launch_bounds__(kT) void k_plane_fold_sum(const double* __restrict__ part, int64_t chunks,
+                                                       double* __restrict__ out) {
+  __shared__ double s[kT];
+  const double* row = part + static_cast<int64_t>(blockIdx.x) * chunks;
+  double acc = 0.0;
+  for (int64_t c0 = 0; c0 < chunks; c0 += kT) {
+    if (c0 + threadIdx.x < chunks) s[threadIdx.x] = row[c0 + threadIdx.x];
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const int m = static_cast<int>(min<int64_t>(kT, chunks - c0));
+      for (int j = 0; j < m; ++j) acc = acc + s[j];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[blockIdx.x] = acc;
+}
+
+}  // namespace prim
+}  // namespace

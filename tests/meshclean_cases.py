@@ -123,6 +123,22 @@ def unreferenced_cases():
     return c
 
 
+def live_case(n):
+    """n triangles that all survive the mapping (every vertex of the 17^3 lattice is alone in its voxel and no
+    triangle repeats an index), so the triple sort and the compaction after it run on exactly n rows.  The last
+    triangle is a rotation of the first: a duplicate whose two copies are n - 1 rows apart, and whose third index
+    after the rotation, the lattice's last vertex, is the largest and no other triangle's -- the two are the last
+    two rows of the first sort's result.  Every 7th triangle in between is a rotation of the one before it."""
+    rng = np.random.default_rng(n)
+    lattice = np.array([[i, j, k] for i in range(17) for j in range(17) for k in range(17)], dtype=np.float64)
+    nv = len(lattice)
+    T = np.stack([rng.permutation(nv - 1)[:3] for _ in range(n)])
+    T[7::7] = T[6:-1:7][:, [1, 2, 0]]
+    T[0] = (5, 6, nv - 1)
+    T[n - 1] = (6, nv - 1, 5)
+    return lattice[rng.permutation(nv)], T.astype(I32), 0.5
+
+
 def simplify_cases():
     """name -> (vertices f64, triangles int32, voxel_size)."""
     c = {}
@@ -149,6 +165,8 @@ def simplify_cases():
     for n in (4095, 4096, 4097):
         T, nv = strip(n, 50 + n)
         c[f"strip_{n}"] = (np.random.default_rng(n).uniform(0.0, 8.0, size=(nv, 3)), T, 0.9)
+    for n in (4095, 4096, 4097):
+        c[f"live_{n}"] = live_case(n)
     c["no_triangles"] = (rng.normal(size=(20, 3)), _t([]), 0.7)
     c["nothing"] = (np.zeros((0, 3)), _t([]), 1.0)
     return c

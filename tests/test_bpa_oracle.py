@@ -150,6 +150,12 @@ def test_the_cases_reach_their_rules():
     s = bo.solved("dense_blob")
     d = s["P"][:, None, :] - s["P"][None, :, :]
     assert len(s["P"]) == 400 and (np.einsum("ijk,ijk->ij", d, d) < 4.0 * s["radii"][0] ** 2).all()
+    # the shuffled sheet's second radius: more candidates than one sort tile (4096) holds, in whatever order
+    # they arrive; ordered by their third index, rows 4095 and 4096 share it, and many share their first two
+    C = np.sort(bo.solved("shuffled")["candidates"][1], 1)
+    third = np.sort(C[:, 2], kind="stable")
+    assert len(C) > 4096 and third[4095] == third[4096]
+    assert len(np.unique(C[:, :2], axis=0)) < len(C) - 1000
     # the duplicates: zero distances
     P = bo.solved("duplicates")["P"]
     assert len(np.unique(P, axis=0)) < len(P)

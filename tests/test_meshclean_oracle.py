@@ -180,6 +180,17 @@ def test_simplify_preconditions():
         info = {}
         V, T2 = oc.simplify_vertex_clustering(P, T, vs, info)
         assert len(T) == n and info["collapsed"] > 0 and 0 < len(T2) < n
+    # the strips above lose triangles before the triple sort (4073 .. 4088 rows reach it: one tile of 4096); these
+    # bring exactly n rows to it, with equal third indices on both sides of row 4096 before and after its first sort
+    for n in (4095, 4096, 4097):
+        P, T, vs = c[f"live_{n}"]
+        info = {}
+        V, T2 = oc.simplify_vertex_clustering(P, T, vs, info)
+        np.testing.assert_array_equal(V, P)
+        assert len(T) == n and info["collapsed"] == 0 and info["duplicates"] > 500 and len(T2) == n - info["duplicates"]
+        rot = np.array([np.roll(t, -int(np.argmin(t))) for t in T])
+        assert rot[0].tolist() == rot[n - 1].tolist() == [5, 6, len(P) - 1] and (rot[1:n - 1, 2] < len(P) - 1).all()
+        assert np.sort(rot[:, 2], kind="stable")[-2:].tolist() == [len(P) - 1] * 2
 
 
 def test_simplify_errors():
@@ -205,5 +216,7 @@ def test_simplify_poisson_sphere(steps):
     assert 0 < len(T2) < len(T) and len(V2) < len(V)
     assert len(T) == len(T2) + info["collapsed"] + info["duplicates"]
     assert info["collapsed"] > 0 and min(info["rotations"]) > 0
+    if steps < 4.0:     # the triple sort and the compaction after it run over more than one tile of 4096 rows
+        assert len(T) - info["collapsed"] > 4096 and len(T2) > 4096
     if steps == 2.0:
         assert info["duplicates"] > 0 and not mo.edge_census(T2)[0]     # not closed: that is the algorithm
