@@ -670,6 +670,42 @@ int sl_write_mesh_ply_device(sl_ctx* ctx, const char* path, const double* vertic
                              const int32_t* triangles, int64_t n_triangles, int64_t chunk_triangles, void* stream);
 int sl_mesh_write_stats(double* stage_ms, int capacity);
 
+/* ---- vertex colours (csrc/slmeshcolor.inl, which states the definition) ----
+ * Open3D's Poisson returns vertex_colors when the cloud has colours and its PLY
+ * writer stores them as uchar red green blue; restated order-free (parity with
+ * Open3D is unpinned; exact against tests/meshcolor_oracle.py).  Blocking on
+ * `stream`; scratch from the merge stage's pool.
+ *   sl_mesh_transfer_colors   cloud_xyz f64 [n][3], cloud_bgr u8 [n][3],
+ *       query_xyz f64 [m][3] (device); n, m < 2^31.  Tier t has radius radius 2^t;
+ *       a query's tier is the first whose open ball holds a cloud point, and its
+ *       colour the blend of the up to k (1..16) points of least (d2, index) in
+ *       that ball with weights d2_first / d2_i, or the first point's colour when
+ *       d2_first == 0.  Tiers run until the radius exceeds the diagonal of the
+ *       joint bounding box, or max_tiers of them (< 0: no cap).  A non-finite
+ *       query, an empty cloud and a query without a point by the last tier get
+ *       fill_bgr (host [3]) and tier 255.  -> out_bgr u8 [m][3], out_tier u8 [m]
+ *       (may be NULL).  A non-finite cloud coordinate, a radius that is not
+ *       finite and positive, k outside 1..16: SL_EINVAL.  m == 0 and n == 0
+ *       succeed.
+ *   sl_mesh_transfer_colors_stats   the calling thread's last call (stats
+ *       [capacity], zero-filled; a measurement aid): [0] tiers run, [1] queries
+ *       filled, [2] host milliseconds in the grid builds, [3] in the query
+ *       passes, [4 + t] queries resolved in tier t, t < 16, [20] tiers that ran
+ *       one wave per query (the upper tiers' kernel; the results are the same).
+ *   sl_write_mesh_ply_colors_device   sl_write_mesh_ply_device with bgr u8
+ *       [n_vertices][3] (device): the header gains property uchar red, green,
+ *       blue after nz and the vertex record has 51 bytes, the six doubles and
+ *       then red green blue from the BGR storage.  Same index check (the path is
+ *       untouched on SL_EINDEX), same ring (its slots hold `chunk_triangles`
+ *       vertices of 51 bytes). */
+int sl_mesh_transfer_colors(sl_ctx* ctx, const double* cloud_xyz, const uint8_t* cloud_bgr, int64_t n,
+                            const double* query_xyz, int64_t m, double radius, int k, int max_tiers,
+                            const uint8_t* fill_bgr, uint8_t* out_bgr, uint8_t* out_tier, void* stream);
+int sl_mesh_transfer_colors_stats(double* stats, int capacity);
+int sl_write_mesh_ply_colors_device(sl_ctx* ctx, const char* path, const double* vertices, int64_t n_vertices,
+                                    const int32_t* triangles, int64_t n_triangles, const uint8_t* bgr,
+                                    int64_t chunk_triangles, void* stream);
+
 /* ---- consistent tangent-plane normal orientation (processing.py:201, :282) ----
  * orient_normals_consistent_tangent_plane restated on the kNN graph alone
  * (csrc/slorient.inl; tests/orient_oracle.py is the CPU restatement, bit for

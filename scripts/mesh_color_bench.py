@@ -1,0 +1,219 @@
+"""Vertex colours (mesh.transfer_colors and the coloured .ply of
+mesh.write_triangle_mesh; csrc/slmeshcolor.inl) on the Poisson mesh of a
+synthetic closed surface: a unit sphere of ``--points`` coloured points with
+outward normals, meshed at ``--depths``.
+
+    python scripts/mesh_color_bench.py                      # depths 8 and 10
+    python scripts/mesh_color_bench.py --depths 8 --reps 5
+    python scripts/mesh_color_bench.py --ab-lib OTHER/libslgpu.so   # + the uncoloured writer, build against build
+
+Prints one JSON line per measurement (milliseconds: the median of ``--reps``
+after one warm-up, wall time around blocking calls, one process):
+  transfer    per depth and case, the drop-ins' parameters (k = 8, radius = twice
+              the cloud's mean nearest-neighbour distance) with the per-tier
+              stats of sl_mesh_transfer_colors_stats.  Case ``full``: the trimmed
+              mesh of the whole sphere.  Case ``hole``: the cloud without the cap
+              z > centre + ``--cap`` and its untrimmed mesh -- Poisson bridges
+              the hole, and the bridge's vertices have no sample nearby, so the
+              upper tiers carry load (the 0.02 trim would cut most of the bridge
+              away again).
+  write       per depth, the coloured .ply against the uncoloured .ply of the
+              same mesh in the same run, alternating, with and without the file.
+  oracle      tests/meshcolor_oracle.transfer_colors on the CPU at a size it
+              finishes, checked against the device result.
+  ab_write    with ``--ab-lib``: write_triangle_mesh without colours on the
+              deepest mesh, this build and the other one in fresh processes that
+              alternate (``--ab-rounds`` each): every process's median, and per
+              build the median and the spread of those.
+"""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+import tempfile
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+
+def timed(fn, reps):
+    """-> the milliseconds of fn() over reps after one warm-up."""
+    import torch
+    ms = []
+    for rep in range(reps + 1):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        if rep:
+            ms.append((time.perf_counter() - t0) * 1e3)
+    return ms
+
+
+def med(ms):
+    return round(statistics.median(ms), 3)
+
+
+def transfer_line(name, P, C, V, radius, reps):
+    from structured_light_for_3d_model_replication_amd import mesh
+    got = {}
+
+    def run():
+        got["out"], got["tier"], got["stats"] = mesh.transfer_colors(P, C, V, radius, k=8, info=True)
+    ms = timed(run, reps)
+    st = got["stats"]
+    tier = got["tier"]
+    used = tier[tier != 255]
+    return {"transfer": name, "reps": reps, "points": len(P), "vertices": len(V), "radius": radius, "k": 8,
+            "ms": med(ms), "ms_min": round(min(ms), 3), "ms_max": round(max(ms), 3),
+            "grid_ms": round(st["grid_ms"], 3), "query_ms": round(st["query_ms"], 3), "tiers": st["tiers"],
+            "wave_tiers": st["wave_tiers"],
+            "highest_tier": int(used.max()) if used.numel() else -1, "filled": st["filled"],
+            "resolved": st["resolved"], "mvertices_per_s": round(len(V) / med(ms) / 1e3, 3)}
+
+
+def write_line(name, V, T, C, d, reps):
+    """The coloured and the uncoloured .ply of one mesh, alternating."""
+    from structured_light_for_3d_model_replication_amd import mesh
+    path = os.path.join(d, "bench.ply")
+    calls = {"plain": lambda: mesh.write_triangle_mesh(path, V, T),
+             "coloured": lambda: mesh.write_triangle_mesh(path, V, T, colors=C),
+             "pack_plain": lambda: mesh._write_device(None, ".ply", V, T),
+             "pack_coloured": lambda: mesh._write_device(None, ".ply", V, T, 0, C)}
+    ms = {k: [] for k in calls}
+    size = {}
+    for rep in range(reps + 1):
+        for k, fn in calls.items():
+            t = timed(fn, 0) if rep == 0 else timed(fn, 1)
+            if rep:
+                ms[k] += t
+            if not k.startswith("pack"):
+                size[k] = os.path.getsize(path)
+    os.remove(path)
+    out = {"write": name, "reps": reps, "vertices": len(V), "triangles": len(T)}
+    for k in calls:
+        out[f"{k}_ms"] = med(ms[k])
+    for k, b in size.items():
+        out[f"{k}_bytes"] = b
+        out[f"{k}_gbps"] = round(b / (out[f"{k}_ms"] * 1e-3) / 1e9, 3)
+    out["coloured_over_plain"] = round(out["coloured_ms"] / out["plain_ms"], 4)
+    return out
+
+
+def oracle_line(n, m):
+    import numpy as np
+
+    from structured_light_for_3d_model_replication_amd import mesh
+    from tests import meshcolor_oracle as vo
+    P, C, Q = vo.random_case(n, m, seed=1)
+    radius = 2.0 * n ** (-1.0 / 3.0) * 0.55
+    t0 = time.perf_counter()
+    want, tier = vo.transfer_colors(P, C, Q, radius)
+    cpu_ms = (time.perf_counter() - t0) * 1e3
+    got = {}
+
+    def run():
+        got["out"], got["tier"] = mesh.transfer_colors(np.array(P), np.array(C), np.array(Q), radius, info=True)[:2]
+    ms = timed(run, 3)
+    equal = bool(np.array_equal(got["out"].cpu().numpy(), want) and np.array_equal(got["tier"].cpu().numpy(), tier))
+    return {"oracle": "tests/meshcolor_oracle.transfer_colors", "points": n, "queries": m, "oracle_ms": round(cpu_ms, 1),
+            "device_ms_with_upload": med(ms), "equal": equal}
+
+
+def ab_child(mesh_file, d, reps):
+    """One process of the A/B: the uncoloured writers on the saved mesh -> one JSON line."""
+    import torch
+
+    from structured_light_for_3d_model_replication_amd import _lib, mesh
+    V, T = torch.load(mesh_file)
+    V, T = V.cuda(), T.cuda()
+    out = {"lib": _lib.LIB_PATH}
+    for ext in (".ply", ".stl"):
+        path = os.path.join(d, f"ab_{os.getpid()}{ext}")
+        ms = timed(lambda: mesh.write_triangle_mesh(path, V, T), reps)
+        out[ext] = {"ms": [round(x, 3) for x in ms], "median": med(ms), "bytes": os.path.getsize(path)}
+        os.remove(path)
+    print(json.dumps(out), flush=True)
+
+
+def ab_write(V, T, d, other, rounds, reps):
+    import torch
+    mesh_file = os.path.join(d, "mesh.pt")
+    torch.save((V.cpu(), T.cpu()), mesh_file)
+    runs = {"this": [], "other": []}
+    for _ in range(rounds):
+        for build in ("other", "this"):
+            env = dict(os.environ)
+            env.pop("SLGPU_LIB", None)
+            if build == "other":
+                env["SLGPU_LIB"] = os.path.abspath(other)
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--ab-child", mesh_file, "--dir", d,
+                                "--reps", str(reps)], env=env, check=True, capture_output=True, text=True)
+            runs[build].append(json.loads(r.stdout.strip().splitlines()[-1]))
+    os.remove(mesh_file)
+    out = {"ab_write": "write_triangle_mesh without colours", "vertices": len(V), "triangles": len(T),
+           "rounds": rounds, "reps": reps, "order": "other, this, other, this, ..."}
+    for ext in (".ply", ".stl"):
+        for build in ("this", "other"):
+            meds = [r[ext]["median"] for r in runs[build]]
+            out[f"{build}{ext}_process_medians_ms"] = meds
+            out[f"{build}{ext}_median_ms"] = med(meds)
+            out[f"{build}{ext}_spread_ms"] = round(max(meds) - min(meds), 3)
+        out[f"this_minus_other{ext}_ms"] = round(out[f"this{ext}_median_ms"] - out[f"other{ext}_median_ms"], 3)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--points", type=int, default=4_000_000)
+    ap.add_argument("--depths", type=int, nargs="*", default=[8, 10])
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--cap", type=float, default=0.97, help="the hole: cloud points with z > centre + this are removed")
+    ap.add_argument("--oracle", type=int, nargs=2, default=[20000, 2000], help="points and queries of the oracle's case")
+    ap.add_argument("--dir", default=None, help="where the files go (default: a temporary directory)")
+    ap.add_argument("--ab-lib", default=None, help="another build of libslgpu.so for the uncoloured writer's A/B")
+    ap.add_argument("--ab-rounds", type=int, default=3)
+    ap.add_argument("--ab-child", default=None, help=argparse.SUPPRESS)
+    a = ap.parse_args()
+    if a.ab_child:
+        ab_child(a.ab_child, a.dir, a.reps)
+        return 0
+    import numpy as np
+    import torch
+
+    from structured_light_for_3d_model_replication_amd import merge, mesh
+    from tests import mesh_oracle as mo
+    centre = (0.1, -0.2, 0.3)
+    Ph, Nh = mo.sphere(a.points, centre)
+    Ch = np.clip((Nh * 127.0 + 128.0), 0, 255).astype(np.uint8)  # a smooth colour field over the sphere
+    P, N, C = torch.from_numpy(Ph).cuda(), torch.from_numpy(Nh).cuda(), torch.from_numpy(Ch).cuda()
+    keep = P[:, 2] <= centre[2] + a.cap
+    Pk, Nk, Ck = P[keep].contiguous(), N[keep].contiguous(), C[keep].contiguous()
+
+    def radius_of(pts):
+        dist = merge.compute_nearest_neighbor_distance(pts)
+        return 2.0 * mesh.ordered_sum(dist) / float(len(pts))
+    r_full, r_hole = radius_of(P), radius_of(Pk)
+    with tempfile.TemporaryDirectory(dir=a.dir) as d:
+        for depth in a.depths:
+            V, T, dens = mesh.create_from_point_cloud_poisson(P, N, depth=depth)
+            V, T = mesh.trim_by_density(V, T, dens, 0.02)
+            del dens
+            print(json.dumps(transfer_line(f"depth_{depth}_full", P, C, V, r_full, a.reps)), flush=True)
+            VC = mesh.transfer_colors(P, C, V, r_full)
+            print(json.dumps(write_line(f"depth_{depth}", V, T, VC, d, a.reps)), flush=True)
+            if a.ab_lib and depth == max(a.depths):
+                print(json.dumps(ab_write(V, T, d, a.ab_lib, a.ab_rounds, a.reps)), flush=True)
+            del V, T, VC
+            V, T, _ = mesh.create_from_point_cloud_poisson(Pk, Nk, depth=depth)
+            print(json.dumps(transfer_line(f"depth_{depth}_hole", Pk, Ck, V, r_hole, a.reps)), flush=True)
+            del V, T
+        print(json.dumps(oracle_line(*a.oracle)), flush=True)
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

@@ -2295,3 +2295,5 @@ int sl_merge_pool_poison(int byte, int64_t* poisoned_bytes) {
 #include "slmeshclean.inl"
 // mesh output: triangle and vertex normals, STL and PLY records packed on the device and streamed to the file
 #include "slmeshwrite.inl"
+// vertex colours: cloud-to-mesh transfer by tiers of nearest samples, the coloured PLY vertex record
+#include "slmeshcolor.inl"

@@ -418,6 +418,53 @@ int write_chunks(sl_ctx* c, const char* what, const char* path, const char* head
   return SL_OK;
 }
 
+// The PLY writer of `what`: the index check, the vertex sums, the header (vertex_props: property lines after nz),
+// then vertex chunks of `vrec`-byte records packed by pack_v(sums, v0, count, dev) and the face chunks.  A slot
+// holds chunk faces, and chunk 50 / 48 vertices of 48 bytes (the STL writer's slots) or chunk vertices of more.
+template <class PackV>
+int write_ply(sl_ctx* c, const char* what, const char* path, const double* vertices, int64_t n_vertices,
+              const int32_t* triangles, int64_t n_triangles, int64_t chunk_triangles, int vrec,
+              const char* vertex_props, PackV pack_v, hipStream_t s) {
+  const std::string name(what);
+  const int64_t chunk = chunk_of(chunk_triangles);
+  if (bad_mesh(vertices, n_vertices, triangles, n_triangles) || chunk < 0)
+    return slgpu_fail(c, SL_EINVAL, (name + ": bad sizes or NULL arguments").c_str());
+  for (double& v : tls_ms) v = 0.0;
+  PoolStream pool_stream(s);
+  MTRY(c, hipSetDevice(slgpu_device(c)));
+  int r = prim::require_indices(c, triangles, n_triangles, n_vertices, (name + ": triangle index out of range").c_str(),
+                               s);
+  if (r) return r;
+  const int64_t vchunk = vrec == kVertexRec ? chunk * kStlRec / kVertexRec : chunk;
+  Ring* ring = nullptr;
+  r = ring_reserve(c, std::max(chunk * kStlRec, vchunk * vrec), &ring);
+  if (r) return r;
+  DBuf<int64_t> sums;
+  MTRY(c, sums.alloc(3 * n_vertices));
+  r = vertex_sums(c, vertices, n_vertices, triangles, n_triangles, sums.p, s);
+  if (r) return r;
+  char head[640];
+  const int hl = snprintf(head, sizeof(head),
+                          "ply\nformat binary_little_endian 1.0\ncomment Created by Open3D\nelement vertex %lld\n"
+                          "property double x\nproperty double y\nproperty double z\n"
+                          "property double nx\nproperty double ny\nproperty double nz\n%s"
+                          "element face %lld\nproperty list uchar uint vertex_indices\nend_header\n",
+                          static_cast<long long>(n_vertices), vertex_props, static_cast<long long>(n_triangles));
+  const int64_t nvc = (n_vertices + vchunk - 1) / vchunk, nfc = (n_triangles + chunk - 1) / chunk;
+  auto v_in = [&](int64_t k) { return std::min(vchunk, n_vertices - k * vchunk); };
+  auto f_in = [&](int64_t k) { return std::min(chunk, n_triangles - k * chunk); };
+  return write_chunks(
+      c, what, path, head, static_cast<size_t>(hl), ring, nvc + nfc,
+      [&](int64_t k, char* dev) {
+        if (k < nvc)
+          pack_v(sums.p, k * vchunk, v_in(k), dev);
+        else
+          hipLaunchKernelGGL(k_mw_pack_faces, dim3(blocks(f_in(k - nvc))), dim3(kT), 0, s, triangles,
+                             (k - nvc) * chunk, f_in(k - nvc), reinterpret_cast<uint4*>(dev));
+      },
+      [&](int64_t k) { return k < nvc ? v_in(k) * vrec : f_in(k - nvc) * kFaceRec; }, s);
+}
+
 }  // namespace mwr
 }  // namespace
 
@@ -501,45 +548,14 @@ int sl_write_mesh_ply_device(sl_ctx* c, const char* path, const double* vertices
                              const int32_t* triangles, int64_t n_triangles, int64_t chunk_triangles, void* stream) {
   using namespace mwr;
   if (!c) return SL_EINVAL;
-  const int64_t chunk = chunk_of(chunk_triangles);
-  if (bad_mesh(vertices, n_vertices, triangles, n_triangles) || chunk < 0)
-    return slgpu_fail(c, SL_EINVAL, "sl_write_mesh_ply_device: bad sizes or NULL arguments");
-  for (double& v : tls_ms) v = 0.0;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  PoolStream pool_stream(s);
-  MTRY(c, hipSetDevice(slgpu_device(c)));
-  int r = prim::require_indices(c, triangles, n_triangles, n_vertices,
-                               "sl_write_mesh_ply_device: triangle index out of range", s);
-  if (r) return r;
-  Ring* ring = nullptr;
-  r = ring_reserve(c, chunk * kStlRec, &ring);  // the slots of the STL writer: chunk faces or chunk 50 / 48 vertices
-  if (r) return r;
-  DBuf<int64_t> sums;
-  MTRY(c, sums.alloc(3 * n_vertices));
-  r = vertex_sums(c, vertices, n_vertices, triangles, n_triangles, sums.p, s);
-  if (r) return r;
-  char head[512];
-  const int hl = snprintf(head, sizeof(head),
-                          "ply\nformat binary_little_endian 1.0\ncomment Created by Open3D\nelement vertex %lld\n"
-                          "property double x\nproperty double y\nproperty double z\n"
-                          "property double nx\nproperty double ny\nproperty double nz\n"
-                          "element face %lld\nproperty list uchar uint vertex_indices\nend_header\n",
-                          static_cast<long long>(n_vertices), static_cast<long long>(n_triangles));
-  const int64_t vchunk = chunk * kStlRec / kVertexRec;
-  const int64_t nvc = (n_vertices + vchunk - 1) / vchunk, nfc = (n_triangles + chunk - 1) / chunk;
-  auto v_in = [&](int64_t k) { return std::min(vchunk, n_vertices - k * vchunk); };
-  auto f_in = [&](int64_t k) { return std::min(chunk, n_triangles - k * chunk); };
-  return write_chunks(
-      c, "sl_write_mesh_ply_device", path, head, static_cast<size_t>(hl), ring, nvc + nfc,
-      [&](int64_t k, char* dev) {
-        if (k < nvc)
-          hipLaunchKernelGGL(k_mw_pack_vertices, dim3(blocks(6 * v_in(k))), dim3(kT), 0, s, vertices, sums.p,
-                             k * vchunk, v_in(k), reinterpret_cast<double*>(dev));
-        else
-          hipLaunchKernelGGL(k_mw_pack_faces, dim3(blocks(f_in(k - nvc))), dim3(kT), 0, s, triangles,
-                             (k - nvc) * chunk, f_in(k - nvc), reinterpret_cast<uint4*>(dev));
+  return write_ply(
+      c, "sl_write_mesh_ply_device", path, vertices, n_vertices, triangles, n_triangles, chunk_triangles, kVertexRec, "",
+      [&](const int64_t* sums, int64_t v0, int64_t count, char* dev) {
+        hipLaunchKernelGGL(k_mw_pack_vertices, dim3(blocks(6 * count)), dim3(kT), 0, s, vertices, sums, v0, count,
+                           reinterpret_cast<double*>(dev));
       },
-      [&](int64_t k) { return k < nvc ? v_in(k) * kVertexRec : f_in(k - nvc) * kFaceRec; }, s);
+      s);
 }
 
 int sl_mesh_write_stats(double* stage_ms, int capacity) {

@@ -40,7 +40,11 @@ are packed into records by HIP kernels and streamed to the file through a ring
 of two pinned chunks (csrc/slmeshwrite.inl states the arithmetic and the
 layout); ``compute_triangle_normals`` and ``compute_vertex_normals`` are the
 normals it writes (the vertex normals as order-free fixed-point sums; exact
-against tests/meshwrite_oracle.py).
+against tests/meshwrite_oracle.py).  ``transfer_colors`` carries a cloud's
+colours onto the mesh vertices -- nearest samples by tiers of doubling radius,
+an inverse-squared-distance blend (csrc/slmeshcolor.inl states the definition;
+exact against tests/meshcolor_oracle.py) -- and ``write_triangle_mesh(...,
+colors=...)`` writes them as ``uchar red green blue`` in the ``.ply``.
 
 Open3D's Poisson is the adaptive-octree variant and is not installed here:
 parity with Open3D is unpinned, and tests/mesh_oracle.py is the CPU restatement
@@ -729,10 +733,11 @@ _VN_FIX = 2.0 ** 40
 _MESH_EXTS = (".stl", ".ply")
 
 
-def _mesh_ply_header(n_vertices: int, n_triangles: int) -> bytes:
+def _mesh_ply_header(n_vertices: int, n_triangles: int, colors: bool = False) -> bytes:
     return (f"ply\nformat binary_little_endian 1.0\ncomment Created by Open3D\nelement vertex {n_vertices}\n"
             "property double x\nproperty double y\nproperty double z\n"
             "property double nx\nproperty double ny\nproperty double nz\n"
+            + ("property uchar red\nproperty uchar green\nproperty uchar blue\n" if colors else "") +
             f"element face {n_triangles}\nproperty list uchar uint vertex_indices\nend_header\n").encode("ascii")
 
 
@@ -763,7 +768,10 @@ def _host_vertex_normals(P, T):
     return out
 
 
-def _write_host(path, ext, vertices, triangles):
+_PLY_COLOR_VERTEX = np.dtype([("pn", "<f8", 6), ("rgb", "u1", 3)])  # 51 bytes, packed
+
+
+def _write_host(path, ext, vertices, triangles, colors=None):
     P = _host(vertices, np.float64)
     T = _host(triangles, np.int64)
     if len(T) and (T.min() < 0 or T.max() >= len(P)):
@@ -772,9 +780,15 @@ def _write_host(path, ext, vertices, triangles):
         rec = np.zeros(len(T), dtype=_PLY_FACE)
         rec["n"] = 3
         rec["v"] = T
+        pn = np.concatenate([P, _host_vertex_normals(P, T)], 1).astype("<f8")
+        if colors is not None:
+            vrec = np.zeros(len(P), dtype=_PLY_COLOR_VERTEX)
+            vrec["pn"] = pn
+            vrec["rgb"] = _host(colors, np.uint8)[:, ::-1]  # BGR storage -> red green blue
+            pn = vrec
         with open(path, "wb") as f:
-            f.write(_mesh_ply_header(len(P), len(T)))
-            np.concatenate([P, _host_vertex_normals(P, T)], 1).astype("<f8").tofile(f)
+            f.write(_mesh_ply_header(len(P), len(T), colors is not None))
+            pn.tofile(f)
             rec.tofile(f)
         return
     p0, p1, p2 = P[T[:, 0]], P[T[:, 1]], P[T[:, 2]]
@@ -788,18 +802,23 @@ def _write_host(path, ext, vertices, triangles):
         rec.tofile(f)
 
 
-def _write_device(path, ext, vertices, triangles, chunk_triangles=0):
-    """The device writers (csrc/slmeshwrite.inl).  ``path`` None: packed and copied back, no file (measurement)."""
+def _write_device(path, ext, vertices, triangles, chunk_triangles=0, colors=None):
+    """The device writers (csrc/slmeshwrite.inl, csrc/slmeshcolor.inl).  ``path`` None: packed and copied back, no
+    file (measurement)."""
     eng, V, T = _mesh_args(vertices, triangles, vertices.device)
     name = "sl_write_mesh_ply_device" if ext == ".ply" else "sl_write_stl_device"
+    extra = ()
+    if colors is not None and ext == ".ply":
+        C = torch.as_tensor(colors).to(device=eng.device, dtype=torch.uint8).contiguous()
+        name, extra = "sl_write_mesh_ply_colors_device", (_ptr(C) if len(C) else None,)
     try:
         _call(eng, name, None if path is None else os.fsencode(path), _ptr(V) if len(V) else None, len(V),
-              _ptr(T) if len(T) else None, len(T), int(chunk_triangles))
+              _ptr(T) if len(T) else None, len(T), *extra, int(chunk_triangles))
     except IndexError:
         raise IndexError("triangle index out of range") from None
 
 
-def write_triangle_mesh(path, vertices, triangles, *, chunk_triangles: int = 0) -> None:
+def write_triangle_mesh(path, vertices, triangles, *, colors=None, chunk_triangles: int = 0) -> None:
     """o3d.io.write_triangle_mesh for ``.stl`` and ``.ply``, after the
     reference's compute_vertex_normals().  ``.stl``: binary STL (80-byte header,
     the count, per triangle the unit normal, three vertices and a zero attribute,
@@ -807,6 +826,11 @@ def write_triangle_mesh(path, vertices, triangles, *, chunk_triangles: int = 0) 
     triangle gets a zero normal.  ``.ply``: Open3D's binary little-endian layout
     (unpinned) -- per vertex six doubles, position and ``compute_vertex_normals``;
     per face the byte 3 and three uint32 -- which keeps the shared vertices.
+    ``colors`` (BGR u8 [V, 3], as the clouds hold them): the ``.ply`` header gains
+    ``property uchar red / green / blue`` after ``nz`` and every vertex record the
+    three bytes (51 in all); an ``.stl`` is written as without them, the format
+    has no colours.  A colour array without one row per vertex raises ValueError
+    before the path is opened.
     Two CUDA tensors on one device are packed on that device and streamed to the
     file through a ring of two pinned chunks of ``chunk_triangles`` triangles (0:
     655 360); anything else (NumPy, CPU tensors) is packed on the host in NumPy.
@@ -815,9 +839,57 @@ def write_triangle_mesh(path, vertices, triangles, *, chunk_triangles: int = 0) 
     ext = os.path.splitext(str(path))[1].lower()
     if ext not in _MESH_EXTS:
         raise ValueError(f"cannot write {path}: only .stl and .ply are supported")
+    if colors is not None and tuple(np.shape(colors) if not hasattr(colors, "shape") else colors.shape) != (
+            len(vertices), 3):
+        raise ValueError("colors must have one row of three per vertex")
     on_device = (isinstance(vertices, torch.Tensor) and isinstance(triangles, torch.Tensor) and vertices.is_cuda
                  and triangles.is_cuda and vertices.device == triangles.device)
     if on_device:
-        _write_device(str(path), ext, vertices, triangles, chunk_triangles)
+        _write_device(str(path), ext, vertices, triangles, chunk_triangles, colors)
     else:
-        _write_host(path, ext, vertices, triangles)
+        _write_host(path, ext, vertices, triangles, colors if ext == ".ply" else None)
+
+
+def transfer_colors(points, colors, vertices, radius, *, k: int = 8, max_tiers=None, fill=(128, 128, 128),
+                    info: bool = False, device=None):
+    """The colours of a cloud carried onto mesh vertices (sl_mesh_transfer_colors;
+    csrc/slmeshcolor.inl states the definition) -> BGR u8 [V, 3] on the device.
+    Tier t searches the open ball of ``radius * 2**t``; a vertex takes, in the
+    first tier whose ball holds a cloud point, the colour of a coincident point
+    (the lowest index) or else the blend of its up to ``k`` (1..16) nearest by
+    (d2, index) with weights d2_first / d2_i.  Tiers run until the radius exceeds
+    the diagonal of the joint bounding box, or ``max_tiers`` of them; a vertex
+    still unresolved, a non-finite vertex and every vertex of an empty cloud get
+    ``fill`` (BGR) and tier 255.  Deviation: Open3D's Poisson colours come from
+    its octree's data field (parity unpinned; exact against
+    tests/meshcolor_oracle.py).  With ``info``: also the tier u8 [V] and the
+    stats dict of ``transfer_colors_stats``."""
+    eng = _engine(device)
+    P = _f64(points, eng.device)
+    Q = _f64(vertices, eng.device)
+    C = torch.as_tensor(colors)
+    if C.dim() != 2 or tuple(C.shape) != (len(P), 3):
+        raise ValueError("colors must have one row of three per point")
+    C = C.to(device=eng.device, dtype=torch.uint8).contiguous()
+    f = (ctypes.c_uint8 * 3)(*[int(x) for x in fill])
+    m = len(Q)
+    out = torch.empty((max(m, 1), 3), dtype=torch.uint8, device=eng.device)
+    tier = torch.empty(max(m, 1), dtype=torch.uint8, device=eng.device)
+    _call(eng, "sl_mesh_transfer_colors", _ptr(P) if len(P) else None, _ptr(C) if len(P) else None, len(P),
+          _ptr(Q) if m else None, m, float(radius), int(k), -1 if max_tiers is None else int(max_tiers), f,
+          _ptr(out), _ptr(tier))
+    if info:
+        return out[:m], tier[:m], transfer_colors_stats(device=eng.device)
+    return out[:m]
+
+
+def transfer_colors_stats(*, device=None) -> dict:
+    """This thread's last ``transfer_colors`` (sl_mesh_transfer_colors_stats; a measurement aid): tiers run,
+    vertices filled, host milliseconds in the grid builds and in the query passes, vertices resolved per tier
+    (the first 16), tiers that ran the one-wave-per-query kernel."""
+    eng = _engine(device)
+    v = (ctypes.c_double * 21)()
+    _lib.check(eng._L.sl_mesh_transfer_colors_stats(v, 21), None, "sl_mesh_transfer_colors_stats")
+    tiers = int(v[0])
+    return {"tiers": tiers, "filled": int(v[1]), "grid_ms": v[2], "query_ms": v[3],
+            "resolved": [int(x) for x in v[4:4 + min(tiers, 16)]], "wave_tiers": int(v[20])}

@@ -43,8 +43,14 @@ errors, and runs them on the GPU through ``merge`` (libslgpu.so):
   (``mesh.select_components``: the islands the trim cuts off and the bubbles
   Poisson closes around stray blobs) and then ``simplify_voxel_size``
   (``mesh.simplify_vertex_clustering``; csrc/slmeshclean.inl).  With all three
-  at their defaults nothing changes.  Only ``.stl`` can be written; a depth whose grids do not
-  fit the device raises MemoryError (depth 10 is the largest).
+  at their defaults nothing changes.  ``.stl`` and ``.ply`` can be written; a depth whose grids do not
+  fit the device raises MemoryError (depth 10 is the largest).  One more keyword-only argument of both,
+  ``vertex_colors=True``, carries the cloud's colours onto the final mesh (after the trim and the clean-up;
+  ``mesh.transfer_colors`` with k = 8 and twice the cloud's mean nearest-neighbour distance,
+  csrc/slmeshcolor.inl) and writes them into a ``.ply``, with one line of the vertex count, the highest tier
+  used and the number filled; an ``.stl`` output or an input without colour properties prints a note and is
+  written as without it.  Deviations: Open3D's Poisson colours come from its octree's data field, and after
+  ``simplify_voxel_size`` it averages the members' colours where this takes the transfer at the vertex.
 
 Without Open3D, "a point cloud object" is a ``Cloud(points, colors)`` of
 device tensors (f64 [N, 3], BGR u8 [N, 3] or None).  It is accepted wherever
@@ -172,15 +178,42 @@ class ProcessingLogic:
     @staticmethod
     def _load_for_meshing(input_path):
         """-> (points, normals | None) on the device (a file that cannot be parsed: an empty cloud)."""
+        return ProcessingLogic._load_colored_for_meshing(input_path)[:2]
+
+    @staticmethod
+    def _load_colored_for_meshing(input_path):
+        """-> (points, normals | None, colours BGR u8 | None) on the device; colours only when the file has colour
+        properties (the zeros a reader fills in for a file without them are not colours)."""
         dev = merge._engine(None).device
         try:
             cloud = ply.read_cloud_device(input_path, device=dev)  # the file read and parsed once
-            P, N = cloud["points"], cloud["normals"]
+            P, N, C = cloud["points"], cloud["normals"], cloud["colors"]
         except (ValueError, KeyError, IndexError):
-            P, N = torch.zeros((0, 3), dtype=torch.float64, device=dev), None
+            P, N, C = torch.zeros((0, 3), dtype=torch.float64, device=dev), None, None
         if len(P) == 0:
             raise ValueError("Point cloud is empty.")
-        return P, N
+        return P, N, C
+
+    @staticmethod
+    def _vertex_colors(tag, output_path, P, C, V, avg_dist=None):
+        """The colours ``vertex_colors=True`` writes: the cloud's, transferred onto the final vertices
+        (mesh.transfer_colors, k = 8, radius = twice the cloud's mean nearest-neighbour distance) -> BGR u8 [V, 3],
+        or None with a one-line note when the output is not a .ply or the input has no colours."""
+        if os.path.splitext(str(output_path))[1].lower() != ".ply":
+            print(f"[{tag}] Vertex colours need a .ply output: written without them.")
+            return None
+        if C is None:
+            print(f"[{tag}] The input has no colours: written without them.")
+            return None
+        if avg_dist is None:
+            distances = merge.compute_nearest_neighbor_distance(P, device=P.device)
+            avg_dist = mesh.ordered_sum(distances, device=P.device) / float(len(distances))
+        radius = 2.0 * avg_dist if avg_dist > 0.0 else 1.0  # (coincident points only: any radius finds them)
+        colors, tier, stats = mesh.transfer_colors(P, C, V, radius, k=8, info=True, device=P.device)
+        used = tier[tier != 255]
+        highest = int(used.max()) if used.numel() else -1
+        print(f"[{tag}] Vertex colours: {len(V)} vertices, highest tier {highest}, {stats['filled']} filled")
+        return colors
 
     @staticmethod
     def _clean_mesh(tag, V, T, keep_largest_component, min_component_triangles, simplify_voxel_size):
@@ -200,12 +233,13 @@ class ProcessingLogic:
     @staticmethod
     def reconstruct_stl(input_path, output_path, mode="watertight", params=None, *, budget_bytes=None,
                         tangent_planes=None, ball_pivoting=False, keep_largest_component=False,
-                        min_component_triangles=None, simplify_voxel_size=None):
+                        min_component_triangles=None, simplify_voxel_size=None, vertex_colors=False):
         if not os.path.exists(input_path):
             raise FileNotFoundError(f"Input file not found: {input_path}")
         params = {} if params is None else params
         print(f"[Recon] Loading {input_path}...")
-        P, N = ProcessingLogic._load_for_meshing(input_path)
+        P, N, C = ProcessingLogic._load_colored_for_meshing(input_path)
+        avg_dist = None
         if N is None:
             print("[Recon] Estimating normals...")
             N = merge.estimate_normals(P, radius=10, max_nn=30, device=P.device)
@@ -245,18 +279,19 @@ class ProcessingLogic:
                                            simplify_voxel_size)
         if len(V) == 0:
             raise ValueError("Generated mesh is empty.")
+        colors = ProcessingLogic._vertex_colors("Recon", output_path, P, C, V, avg_dist) if vertex_colors else None
         print("[Recon] Computing normals and saving...")
-        mesh.write_triangle_mesh(output_path, V, T)
+        mesh.write_triangle_mesh(output_path, V, T, colors=colors)
         print(f"[Recon] Saved STL to {output_path}")
 
     @staticmethod
     def mesh_360(input_path, output_path, depth=10, density_trim=0.01, orientation_mode="tangent", *,
                  budget_bytes=None, tangent_planes=None, keep_largest_component=False, min_component_triangles=None,
-                 simplify_voxel_size=None):
+                 simplify_voxel_size=None, vertex_colors=False):
         if not os.path.exists(input_path):
             raise FileNotFoundError(f"Input file not found: {input_path}")
         print(f"[360 Mesh] Loading {input_path}...")
-        P, _ = ProcessingLogic._load_for_meshing(input_path)
+        P, _, C = ProcessingLogic._load_colored_for_meshing(input_path)
         print("[360 Mesh] Estimating normals...")
         N = merge.estimate_normals(P, radius=0.1, max_nn=30, device=P.device)
         print(f"[360 Mesh] Re-orienting normals (Mode: {orientation_mode})...")
@@ -291,7 +326,8 @@ class ProcessingLogic:
             print("[360 Mesh] Density trim is 0.0 -> Keeping watertight result.")
         V, T = ProcessingLogic._clean_mesh("360 Mesh", V, T, keep_largest_component, min_component_triangles,
                                            simplify_voxel_size)
-        mesh.write_triangle_mesh(output_path, V, T)
+        colors = ProcessingLogic._vertex_colors("360 Mesh", output_path, P, C, V) if vertex_colors else None
+        mesh.write_triangle_mesh(output_path, V, T, colors=colors)
         print(f"[360 Mesh] Saved to {output_path}")
 
 
