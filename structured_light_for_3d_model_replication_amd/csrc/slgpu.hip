@@ -68,6 +68,7 @@
 
 #include "rccl/rccl.h"
 #include "slgpu.h"
+#include "slstream.h"
 
 #pragma clang fp contract(off)
 
@@ -2262,10 +2263,9 @@ struct sl_ctx {
   int* d_plyr_cols = nullptr;
   int64_t cap_plyr_cols = 0;
   int64_t cap_gcounts = 0;
-  // sl_write_stl_device / sl_write_mesh_ply_device (slmeshwrite.inl): the ring of device and pinned chunk
-  // slots, owned by that file (slgpu_mesh_ring) and released with the context
-  void* mesh_ring = nullptr;
-  void (*mesh_ring_release)(void*) = nullptr;
+  // the ring of chunk slots the mesh writers stream through (slstream.h): sl_write_stl_device,
+  // sl_write_mesh_ply_device, sl_write_mesh_ply_colors_device
+  slstream::Ring file_ring;
   // the last call's stream: a call on another stream first waits for the work
   // queued there (the scratch above is per context)
   hipStream_t last_stream = nullptr;
@@ -2799,9 +2799,10 @@ int stream_handoff(sl_ctx* c, hipStream_t s) {
 
 }  // namespace
 
-// helpers for slmerge.hip (same library)
+// helpers for slmerge.hip and slstream.h (same library)
 int slgpu_fail(sl_ctx* c, int code, const char* msg) { return fail(c, code, msg); }
 int slgpu_device(const sl_ctx* c) { return c->device; }
+slstream::Ring* slgpu_file_ring(sl_ctx* c) { return &c->file_ring; }
 
 // ------------------------------------------------------------- PLY writer ----
 // The ASCII PLY of sl_system.py:665-691 (== multi_point_cloud_process.py:
@@ -2907,7 +2908,7 @@ char* fmt4(char* o, double x) {
 
 __host__ __device__ inline int u8_len(unsigned v) { return v >= 100 ? 3 : v >= 10 ? 2 : 1; }
 
-__host__ __device__ inline char* fmt_u8_hd(char* o, unsigned v) {
+__host__ __device__ inline char* fmt_u8(char* o, unsigned v) {
   if (v >= 100) *o++ = static_cast<char>('0' + v / 100u);
   if (v >= 10) *o++ = static_cast<char>('0' + v / 10u % 10u);
   *o++ = static_cast<char>('0' + v % 10u);
@@ -2923,19 +2924,12 @@ __host__ __device__ inline char* ply_line(char* o, double x, double y, double z,
   *o++ = ' ';
   o = fmt4_digits(o, z);
   *o++ = ' ';
-  o = fmt_u8_hd(o, r);
+  o = fmt_u8(o, r);
   *o++ = ' ';
-  o = fmt_u8_hd(o, g);
+  o = fmt_u8(o, g);
   *o++ = ' ';
-  o = fmt_u8_hd(o, b);
+  o = fmt_u8(o, b);
   *o++ = '\n';
-  return o;
-}
-
-char* fmt_u8(char* o, unsigned v) {
-  if (v >= 100) *o++ = static_cast<char>('0' + v / 100u);
-  if (v >= 10) *o++ = static_cast<char>('0' + v / 10u % 10u);
-  *o++ = static_cast<char>('0' + v % 10u);
   return o;
 }
 
@@ -3056,6 +3050,16 @@ __global__ __launch_bounds__(kPlyBlock) void k_ply_text(const T* xyz, const uint
   for (unsigned j = threadIdx.x; j < total; j += kPlyBlock) dst[j] = s_txt[j];
 }
 
+// the ASCII file's header for n points (the host formatter's and the device writer's)
+std::string ply_ascii_header(int64_t n) {
+  char hb[256];
+  snprintf(hb, sizeof(hb),
+           "ply\nformat ascii 1.0\nelement vertex %lld\nproperty float x\nproperty float y\n"
+           "property float z\nproperty uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n",
+           static_cast<long long>(n));
+  return hb;
+}
+
 // Header + the point lines in `threads` contiguous parts (formatted in
 // parallel) into per-part buffers kept across calls (grown, never zero-filled:
 // a fresh 64-B-per-point buffer of a 4K view is ~420 MB whose zero fill and
@@ -3066,65 +3070,6 @@ struct PlyParts {
   std::vector<const char*> ptr;
   std::vector<size_t> len;
 };
-// open(path) for writing from byte 0, as open(O_TRUNC) does -- except that a
-// large regular file already there (a re-run over the same scan folder) is
-// renamed away first and unlinked on another thread: truncating a 250-MB
-// file's cached pages in the writer's path had cost 40 ms per file (66 ms
-// against 26 for a new file; rename + the unlink beside the write 27 ms,
-// scripts/dbg/overwrite_cost.py).  The new file takes the old one's mode.
-// Symlinks, files with other hard links, files of another owner and small
-// files are truncated in place, as open(..., 'w') does.  The unlinks still
-// pending when the process exits are waited for (10 s at most).
-struct PlyReaper {
-  std::mutex m;
-  std::condition_variable cv;
-  int pending = 0;
-  unsigned long seq = 0;
-  const pid_t owner = getpid();  // (a forked child has none of the unlink threads: it does not wait)
-  ~PlyReaper() {
-    if (getpid() != owner) return;
-    std::unique_lock<std::mutex> lk(m);
-    cv.wait_for(lk, std::chrono::seconds(10), [this] { return pending == 0; });
-  }
-};
-PlyReaper& ply_reaper() {
-  static PlyReaper r;
-  return r;
-}
-int open_replacing(const char* path) {
-  struct stat st;
-  if (lstat(path, &st) == 0 && S_ISREG(st.st_mode) && st.st_nlink == 1 && st.st_uid == geteuid() &&
-      st.st_size >= (16 << 20)) {
-    PlyReaper& r = ply_reaper();
-    unsigned long k;
-    {
-      std::lock_guard<std::mutex> lk(r.m);
-      k = r.seq++;
-    }
-    std::string old = std::string(path) + ".slgpu-old-" + std::to_string(getpid()) + "-" + std::to_string(k);
-    if (rename(path, old.c_str()) == 0) {
-      const int fd = open(path, O_WRONLY | O_CREAT | O_EXCL | O_CLOEXEC, st.st_mode & 07777);
-      if (fd < 0) {  // (the path reappeared meanwhile): the old file back, and the plain route
-        rename(old.c_str(), path);
-      } else {
-        fchmod(fd, st.st_mode & 07777);  // (the mode, whatever the umask)
-        {
-          std::lock_guard<std::mutex> lk(r.m);
-          ++r.pending;
-        }
-        std::thread([&r, old]() {
-          unlink(old.c_str());
-          std::lock_guard<std::mutex> lk(r.m);
-          --r.pending;
-          r.cv.notify_all();
-        }).detach();
-        return fd;
-      }
-    }
-  }
-  return open(path, O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0666);
-}
-
 std::mutex& ply_mutex() {
   static std::mutex m;
   return m;
@@ -3132,12 +3077,7 @@ std::mutex& ply_mutex() {
 void ply_format(const void* xyz, int xyz_dtype, const uint8_t* bgr, int64_t n, int threads, PlyParts& out) {
   static std::vector<std::unique_ptr<char[]>> bufs;  // guarded by ply_mutex()
   static std::vector<size_t> caps;
-  char hb[256];
-  snprintf(hb, sizeof(hb),
-           "ply\nformat ascii 1.0\nelement vertex %lld\nproperty float x\nproperty float y\n"
-           "property float z\nproperty uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n",
-           static_cast<long long>(n));
-  out.head = hb;
+  out.head = ply_ascii_header(n);
   const int T = static_cast<int>(
       std::max<int64_t>(1, std::min<int64_t>(threads > 0 ? threads : 1, (n + 65535) / 65536)));
   if (static_cast<int>(bufs.size()) < T) {
@@ -3190,11 +3130,69 @@ void ply_format(const void* xyz, int xyz_dtype, const uint8_t* bgr, int64_t n, i
 
 }  // namespace
 
-// for slmerge.hip (slmeshwrite.inl): the mesh writers open their files as the PLY writers do
-int slgpu_open_replacing(const char* path) { return open_replacing(path); }
-void** slgpu_mesh_ring(sl_ctx* c, void (*release)(void*)) {
-  c->mesh_ring_release = release;
-  return &c->mesh_ring;
+// open(path) for writing from byte 0, as open(O_TRUNC) does -- except that a
+// large regular file already there (a re-run over the same scan folder) is
+// renamed away first and unlinked on another thread: truncating a 250-MB
+// file's cached pages in the writer's path had cost 40 ms per file (66 ms
+// against 26 for a new file; rename + the unlink beside the write 27 ms,
+// scripts/dbg/overwrite_cost.py).  The new file takes the old one's mode.
+// Symlinks, files with other hard links, files of another owner and small
+// files are truncated in place, as open(..., 'w') does.  The unlinks still
+// pending when the process exits are waited for (10 s at most); the state they
+// touch is on the heap and never destroyed, so a thread that outlasts the wait
+// still finds its mutex.
+namespace {
+struct PlyReaper {
+  std::mutex m;
+  std::condition_variable cv;
+  int pending = 0;
+  unsigned long seq = 0;
+  const pid_t owner = getpid();  // (a forked child has none of the unlink threads: it does not wait)
+};
+PlyReaper& ply_reaper() {
+  static PlyReaper* const r = new PlyReaper();
+  static const struct AtExit {
+    ~AtExit() {
+      if (getpid() != r->owner) return;
+      std::unique_lock<std::mutex> lk(r->m);
+      r->cv.wait_for(lk, std::chrono::seconds(10), [] { return r->pending == 0; });
+    }
+  } wait_at_exit;
+  return *r;
+}
+}  // namespace
+int slgpu_open_replacing(const char* path) {
+  struct stat st;
+  if (lstat(path, &st) == 0 && S_ISREG(st.st_mode) && st.st_nlink == 1 && st.st_uid == geteuid() &&
+      st.st_size >= (16 << 20)) {
+    PlyReaper& r = ply_reaper();
+    unsigned long k;
+    {
+      std::lock_guard<std::mutex> lk(r.m);
+      k = r.seq++;
+    }
+    std::string old = std::string(path) + ".slgpu-old-" + std::to_string(getpid()) + "-" + std::to_string(k);
+    if (rename(path, old.c_str()) == 0) {
+      const int fd = open(path, O_WRONLY | O_CREAT | O_EXCL | O_CLOEXEC, st.st_mode & 07777);
+      if (fd < 0) {  // (the path reappeared meanwhile): the old file back, and the plain route
+        rename(old.c_str(), path);
+      } else {
+        fchmod(fd, st.st_mode & 07777);  // (the mode, whatever the umask)
+        {
+          std::lock_guard<std::mutex> lk(r.m);
+          ++r.pending;
+        }
+        std::thread([&r, old]() {
+          unlink(old.c_str());
+          std::lock_guard<std::mutex> lk(r.m);
+          --r.pending;
+          r.cv.notify_all();
+        }).detach();
+        return fd;
+      }
+    }
+  }
+  return open(path, O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0666);
 }
 
 extern "C" {
@@ -3241,7 +3239,7 @@ void sl_ctx_destroy(sl_ctx* c) {
                     static_cast<void*>(c->d_plyr_cols)})
     if (ptr) (void)hipFree(ptr);
   if (c->h_ply_text) (void)hipHostFree(c->h_ply_text);
-  if (c->mesh_ring && c->mesh_ring_release) c->mesh_ring_release(c->mesh_ring);
+  slstream::ring_release(&c->file_ring);
   if (c->done_ev) (void)hipEventDestroy(c->done_ev);
   for (hipEvent_t e : c->prof_ev) (void)hipEventDestroy(e);
   for (void* ptr : {static_cast<void*>(c->d_planes), static_cast<void*>(c->d_xn), static_cast<void*>(c->d_yn),
@@ -3853,20 +3851,10 @@ int sl_write_ply(const char* path, const void* xyz, int xyz_dtype, const uint8_t
   std::lock_guard<std::mutex> lk(ply_mutex());
   PlyParts parts;
   ply_format(xyz, xyz_dtype, bgr, n, threads, parts);
-  const int fd = open_replacing(path);
+  const int fd = slgpu_open_replacing(path);
   if (fd < 0) return SL_EIO;
-  auto put = [fd](const char* p, size_t len) -> bool {
-    while (len) {
-      const ssize_t w = write(fd, p, len);
-      if (w < 0 && errno == EINTR) continue;
-      if (w <= 0) return false;
-      p += w;
-      len -= static_cast<size_t>(w);
-    }
-    return true;
-  };
-  bool ok = put(parts.head.data(), parts.head.size());
-  for (size_t t = 0; ok && t < parts.len.size(); ++t) ok = put(parts.ptr[t], parts.len[t]);
+  bool ok = slstream::put_all(fd, parts.head.data(), parts.head.size());
+  for (size_t t = 0; ok && t < parts.len.size(); ++t) ok = slstream::put_all(fd, parts.ptr[t], parts.len[t]);
   ok = (close(fd) == 0) && ok;
   return ok ? SL_OK : SL_EIO;
 }
@@ -3934,12 +3922,7 @@ int sl_write_ply_device(sl_ctx* c, const char* path, const void* xyz, int xyz_dt
     HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_ply_text), static_cast<size_t>(total)));
     c->cap_h_ply_text = total;
   }
-  char hb[256];
-  const int hl = snprintf(hb, sizeof(hb),
-                          "ply\nformat ascii 1.0\nelement vertex %lld\nproperty float x\nproperty float y\n"
-                          "property float z\nproperty uchar red\nproperty uchar green\nproperty uchar blue\n"
-                          "end_header\n",
-                          static_cast<long long>(n));
+  const std::string head = ply_ascii_header(n);
   // the text back in chunks (events on the stream), each written as it lands
   constexpr int64_t kChunkBytes = int64_t{32} << 20;
   const int nch = static_cast<int>(std::max<int64_t>(1, (total + kChunkBytes - 1) / kChunkBytes));
@@ -3952,24 +3935,15 @@ int sl_write_ply_device(sl_ctx* c, const char* path, const void* xyz, int xyz_dt
                                      hipMemcpyDeviceToHost, s) == hipSuccess) &&
          hipEventRecord(evs[k], s) == hipSuccess;
   }
-  const int fd = ok ? open_replacing(path) : -1;
-  auto put = [fd](const char* p, size_t len) -> bool {
-    while (len) {
-      const ssize_t w = write(fd, p, len);
-      if (w < 0 && errno == EINTR) continue;
-      if (w <= 0) return false;
-      p += w;
-      len -= static_cast<size_t>(w);
-    }
-    return true;
-  };
-  bool io_ok = fd >= 0 && put(hb, static_cast<size_t>(hl));
+  const int fd = ok ? slgpu_open_replacing(path) : -1;
+  bool io_ok = fd >= 0 && slstream::put_all(fd, head.data(), head.size());
   for (int k = 0; k < nch; ++k) {
     const int64_t lo = k * kChunkBytes, len = std::min(total, lo + kChunkBytes) - lo;
     const bool landed = evs[k] && hipEventSynchronize(evs[k]) == hipSuccess;
     ok = ok && landed;
-    if (io_ok && landed && len > 0) io_ok = put(c->h_ply_text + lo, static_cast<size_t>(len));
+    if (io_ok && landed && len > 0) io_ok = slstream::put_all(fd, c->h_ply_text + lo, static_cast<size_t>(len));
   }
+  if (!ok) (void)hipStreamSynchronize(s);  // a copy queued without its event may still be writing h_ply_text
   for (hipEvent_t e : evs)
     if (e) (void)hipEventDestroy(e);
   if (fd >= 0) io_ok = (close(fd) == 0) && io_ok;
@@ -4014,15 +3988,10 @@ int sl_write_ply_binary(const char* path, const void* xyz, int xyz_dtype, const 
   for (int t = 1; t < T; ++t) pool.emplace_back(work, t);
   work(0);
   for (auto& th : pool) th.join();
-  const int fd = open_replacing(path);
-  FILE* f = fd >= 0 ? fdopen(fd, "wb") : nullptr;
-  if (!f) {
-    if (fd >= 0) close(fd);
-    return SL_EIO;
-  }
-  bool ok = fwrite(hb, 1, static_cast<size_t>(hl), f) == static_cast<size_t>(hl);
-  if (ok && n) ok = fwrite(body.data(), 1, body.size(), f) == body.size();
-  ok = (fclose(f) == 0) && ok;
+  const int fd = slgpu_open_replacing(path);
+  if (fd < 0) return SL_EIO;
+  bool ok = slstream::put_all(fd, hb, static_cast<size_t>(hl)) && slstream::put_all(fd, body.data(), body.size());
+  ok = (close(fd) == 0) && ok;
   return ok ? SL_OK : SL_EIO;
 }
 

@@ -35,11 +35,11 @@
 #include <vector>
 
 #include "slgpu.h"
+#include "slstream.h"  // (declares slgpu_fail, slgpu_open_replacing, slgpu_file_ring)
 
 #pragma clang fp contract(off)
 
 // from slgpu.hip
-int slgpu_fail(sl_ctx* c, int code, const char* msg);
 int slgpu_device(const sl_ctx* c);
 
 namespace {

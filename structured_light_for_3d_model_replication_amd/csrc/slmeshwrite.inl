@@ -58,31 +58,16 @@
 // The threads of a wave read every second (fourth) index triple; the waves of
 // the workgroup touch the same lines, which the vector cache serves.
 //
-// Streaming.  The body never exists as a whole: a ring of kRing slots, each a
-// device buffer and a pinned host buffer of one chunk (default 655 360
-// triangles, 32 768 000 B), allocated once per context and kept (they grow only
-// when a larger chunk is asked for, up to kMaxChunkTriangles).  On the caller's
-// stream chunk k is packed into device slot k mod kRing, copied to pinned slot k
-// mod kRing and followed by an event; the host writes chunk k after its event,
-// and chunk k + kRing is queued only after chunk k has been written.  Staging is
-// kRing (slot + slot) bytes whatever T is; the PLY writer also holds the 24 V
-// bytes of the vertex sums.  After a failed launch, copy or write nothing more is
-// queued, and what was queued is waited for before the call returns.
+// Streaming.  The body never exists as a whole: the records go through the context's ring of chunk slots
+// (slstream.h states the order), kRing slots of one chunk (default 655 360 triangles, 32 768 000 B; they grow only
+// when a larger chunk is asked for, up to kMaxChunkTriangles).  Chunk k is packed into device slot k mod kRing.
+// Staging is kRing (slot + slot) bytes whatever T is; the PLY writer also holds the 24 V bytes of the vertex sums.
 
-#include <errno.h>
-#include <unistd.h>
-
-#include <chrono>
 #include <string>
-
-// from slgpu.hip: open_replacing, and the context's slot for the ring below (freed with the context by `release`)
-int slgpu_open_replacing(const char* path);
-void** slgpu_mesh_ring(sl_ctx* c, void (*release)(void*));
 
 namespace {
 namespace mwr {
 
-constexpr int kRing = 2;
 constexpr int64_t kChunkTriangles = 655360;                      // 32 768 000 B of STL records
 constexpr int64_t kMaxChunkTriangles = 8 * kChunkTriangles;
 constexpr int kStlRec = 50, kFaceRec = 13, kVertexRec = 48;
@@ -280,83 +265,6 @@ __global__ __launch_bounds__(kT) void k_mw_pack_vertices(const double* __restric
 }
 
 // ---- host
-struct Ring {
-  char* dev[kRing] = {};
-  char* pin[kRing] = {};
-  hipEvent_t ev[kRing] = {};
-  int64_t cap = 0;  // bytes of every slot
-};
-
-void ring_drop_slots(Ring* r) {
-  for (int i = 0; i < kRing; ++i) {
-    if (r->dev[i]) (void)hipFree(r->dev[i]);
-    if (r->pin[i]) (void)hipHostFree(r->pin[i]);
-    r->dev[i] = r->pin[i] = nullptr;
-  }
-  r->cap = 0;
-}
-
-void ring_release(void* p) {
-  Ring* r = static_cast<Ring*>(p);
-  ring_drop_slots(r);
-  for (hipEvent_t e : r->ev)
-    if (e) (void)hipEventDestroy(e);
-  delete r;
-}
-
-// The context's ring with slots of at least `bytes` (idle between calls: a writer waits for all it queued).
-int ring_reserve(sl_ctx* c, int64_t bytes, Ring** out) {
-  void** slot = slgpu_mesh_ring(c, ring_release);
-  if (!*slot) *slot = new Ring();
-  Ring* r = static_cast<Ring*>(*slot);
-  for (hipEvent_t& e : r->ev)
-    if (!e) MTRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  if (r->cap < bytes) {
-    ring_drop_slots(r);
-    for (int i = 0; i < kRing; ++i) {
-      MTRY(c, hipMalloc(reinterpret_cast<void**>(&r->dev[i]), static_cast<size_t>(bytes)));
-      MTRY(c, hipHostMalloc(reinterpret_cast<void**>(&r->pin[i]), static_cast<size_t>(bytes), hipHostMallocDefault));
-    }
-    r->cap = bytes;
-  }
-  *out = r;
-  return SL_OK;
-}
-
-// The ring's order.  enqueue(k, slot): chunk k's work and the slot's event onto the stream; landed(slot): wait
-// for that event; sink(k, slot): consume the pinned slot.  Chunk k + ring is queued only after chunk k was
-// consumed; after a failure nothing more is queued, and everything queued is still waited for.
-template <class Enqueue, class Landed, class Sink>
-int stream_chunks(int64_t n_chunks, int ring, Enqueue enqueue, Landed landed, Sink sink) {
-  int64_t queued = 0;
-  bool dev_ok = true, io_ok = true;
-  for (int64_t k = 0; k < n_chunks; ++k) {
-    while (dev_ok && io_ok && queued < n_chunks && queued < k + ring) {
-      dev_ok = enqueue(queued, static_cast<int>(queued % ring));
-      if (dev_ok) ++queued;
-    }
-    if (k >= queued) break;
-    dev_ok = landed(static_cast<int>(k % ring)) && dev_ok;
-    if (dev_ok && io_ok) io_ok = sink(k, static_cast<int>(k % ring));
-  }
-  return !dev_ok ? SL_EHIP : !io_ok ? SL_EIO : SL_OK;
-}
-
-bool put_all(int fd, const char* p, size_t len) {
-  while (len) {
-    const ssize_t w = write(fd, p, len);
-    if (w < 0 && errno == EINTR) continue;
-    if (w <= 0) return false;
-    p += w;
-    len -= static_cast<size_t>(w);
-  }
-  return true;
-}
-
-double ms_since(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 bool bad_mesh(const double* vertices, int64_t n_v, const int32_t* triangles, int64_t n_t) {
   return n_v < 0 || n_t < 0 || n_v >= (1ll << 31) || n_t >= (1ll << 31) || (n_v && !vertices) || (n_t && !triangles);
 }
@@ -379,45 +287,6 @@ int vertex_sums(sl_ctx* c, const double* vertices, int64_t n_v, const int32_t* t
   return SL_OK;
 }
 
-// The file (path NULL: no file, everything else the same -- a measurement aid): `head`, then the chunks.
-// pack(k, dev): chunk k's kernels onto `s`; bytes(k): its size.
-template <class Pack, class Bytes>
-int write_chunks(sl_ctx* c, const char* what, const char* path, const char* head, size_t head_len, Ring* ring,
-                 int64_t n_chunks, Pack pack, Bytes bytes, hipStream_t s) {
-  const auto t_all = std::chrono::steady_clock::now();
-  const int fd = path ? slgpu_open_replacing(path) : -1;
-  if (path && fd < 0) return slgpu_fail(c, SL_EIO, (std::string(what) + ": cannot open the file").c_str());
-  bool io_ok = !path || put_all(fd, head, head_len);
-  const int r = stream_chunks(
-      io_ok ? n_chunks : 0, kRing,
-      [&](int64_t k, int slot) {
-        pack(k, ring->dev[slot]);
-        return hipGetLastError() == hipSuccess &&
-               hipMemcpyAsync(ring->pin[slot], ring->dev[slot], static_cast<size_t>(bytes(k)), hipMemcpyDeviceToHost,
-                              s) == hipSuccess &&
-               hipEventRecord(ring->ev[slot], s) == hipSuccess;
-      },
-      [&](int slot) {
-        const auto t0 = std::chrono::steady_clock::now();
-        const bool ok = hipEventSynchronize(ring->ev[slot]) == hipSuccess;
-        tls_ms[0] += ms_since(t0);
-        return ok;
-      },
-      [&](int64_t k, int slot) {
-        if (!path) return true;
-        const auto t0 = std::chrono::steady_clock::now();
-        const bool ok = put_all(fd, ring->pin[slot], static_cast<size_t>(bytes(k)));
-        tls_ms[1] += ms_since(t0);
-        return ok;
-      });
-  if (r == SL_EHIP) (void)hipStreamSynchronize(s);  // a half-queued chunk may still be writing its slot
-  if (fd >= 0) io_ok = (close(fd) == 0) && io_ok;
-  tls_ms[2] = ms_since(t_all);
-  if (r == SL_EHIP) return slgpu_fail(c, SL_EHIP, (std::string(what) + ": packing or copying failed").c_str());
-  if (r == SL_EIO || !io_ok) return slgpu_fail(c, SL_EIO, (std::string(what) + ": writing the file failed").c_str());
-  return SL_OK;
-}
-
 // The PLY writer of `what`: the index check, the vertex sums, the header (vertex_props: property lines after nz),
 // then vertex chunks of `vrec`-byte records packed by pack_v(sums, v0, count, dev) and the face chunks.  A slot
 // holds chunk faces, and chunk 50 / 48 vertices of 48 bytes (the STL writer's slots) or chunk vertices of more.
@@ -436,9 +305,8 @@ int write_ply(sl_ctx* c, const char* what, const char* path, const double* verti
                                s);
   if (r) return r;
   const int64_t vchunk = vrec == kVertexRec ? chunk * kStlRec / kVertexRec : chunk;
-  Ring* ring = nullptr;
-  r = ring_reserve(c, std::max(chunk * kStlRec, vchunk * vrec), &ring);
-  if (r) return r;
+  slstream::Ring* ring = slgpu_file_ring(c);
+  MTRY(c, slstream::ring_reserve(ring, std::max(chunk * kStlRec, vchunk * vrec)));
   DBuf<int64_t> sums;
   MTRY(c, sums.alloc(3 * n_vertices));
   r = vertex_sums(c, vertices, n_vertices, triangles, n_triangles, sums.p, s);
@@ -453,7 +321,7 @@ int write_ply(sl_ctx* c, const char* what, const char* path, const double* verti
   const int64_t nvc = (n_vertices + vchunk - 1) / vchunk, nfc = (n_triangles + chunk - 1) / chunk;
   auto v_in = [&](int64_t k) { return std::min(vchunk, n_vertices - k * vchunk); };
   auto f_in = [&](int64_t k) { return std::min(chunk, n_triangles - k * chunk); };
-  return write_chunks(
+  return slstream::write_chunks(
       c, what, path, head, static_cast<size_t>(hl), ring, nvc + nfc,
       [&](int64_t k, char* dev) {
         if (k < nvc)
@@ -462,7 +330,7 @@ int write_ply(sl_ctx* c, const char* what, const char* path, const double* verti
           hipLaunchKernelGGL(k_mw_pack_faces, dim3(blocks(f_in(k - nvc))), dim3(kT), 0, s, triangles,
                              (k - nvc) * chunk, f_in(k - nvc), reinterpret_cast<uint4*>(dev));
       },
-      [&](int64_t k) { return k < nvc ? v_in(k) * vrec : f_in(k - nvc) * kFaceRec; }, s);
+      [&](int64_t k) { return k < nvc ? v_in(k) * vrec : f_in(k - nvc) * kFaceRec; }, s, tls_ms);
 }
 
 }  // namespace mwr
@@ -527,21 +395,20 @@ int sl_write_stl_device(sl_ctx* c, const char* path, const double* vertices, int
   int r = prim::require_indices(c, triangles, n_triangles, n_vertices, "sl_write_stl_device: triangle index out of range",
                                s);
   if (r) return r;
-  Ring* ring = nullptr;
-  r = ring_reserve(c, chunk * kStlRec, &ring);
-  if (r) return r;
+  slstream::Ring* ring = slgpu_file_ring(c);
+  MTRY(c, slstream::ring_reserve(ring, chunk * kStlRec));
   char head[84] = {};
   const uint32_t count = static_cast<uint32_t>(n_triangles);
   memcpy(head + 80, &count, 4);
   const int64_t n_chunks = (n_triangles + chunk - 1) / chunk;
   auto in_chunk = [&](int64_t k) { return std::min(chunk, n_triangles - k * chunk); };
-  return write_chunks(
+  return slstream::write_chunks(
       c, "sl_write_stl_device", path, head, sizeof(head), ring, n_chunks,
       [&](int64_t k, char* dev) {
         hipLaunchKernelGGL(k_mw_pack_stl, dim3(blocks(in_chunk(k))), dim3(kT), 0, s, vertices, triangles, k * chunk,
                            in_chunk(k), reinterpret_cast<uint4*>(dev));
       },
-      [&](int64_t k) { return in_chunk(k) * kStlRec; }, s);
+      [&](int64_t k) { return in_chunk(k) * kStlRec; }, s, tls_ms);
 }
 
 int sl_write_mesh_ply_device(sl_ctx* c, const char* path, const double* vertices, int64_t n_vertices,

@@ -3,7 +3,13 @@ is byte-identical to the host formatter (ply.ply_text), whose bytes are pinned
 against the reference's own PLY files and CPython's %.4f (tests/test_ply_io.py):
 random and edge values in f64 and f32 (ties, signed zeros, tiny and 8.99e11
 magnitudes, every colour width), the empty cloud, and clouds the device hands
-back to the host (NaN, inf, |x| >= 9e11: libc's %.4f)."""
+back to the host (NaN, inf, |x| >= 9e11: libc's %.4f).
+
+The text goes back to the host in chunks of 32 MiB: files of one, two, three
+and four chunks with the boundaries placed by 32-byte lines, the cloud writer
+between mesh writes on one context while the mesh writers' ring slots
+(csrc/slstream.h) grow, a path that cannot be opened, and the host fallback
+between two device-formatted writes."""
 import numpy as np
 import pytest
 import torch
@@ -97,3 +103,110 @@ def test_device_ply_replaces_an_existing_file(tmp_path):
             break
         time.sleep(0.05)
     assert [p.name for p in tmp_path.iterdir()] == ["scan.ply"]
+
+
+# ---- chunks -----------------------------------------------------------------------------------------------------
+CHUNK_LINES = 1 << 20   # a 32 MiB chunk of 32-byte lines
+
+
+def _same(a, b):
+    """a == b without pytest's comparison report (the files are up to 100 MB)."""
+    return a == b
+
+
+@pytest.fixture(scope="module")
+def fixed_width_cloud():
+    """3 * 2^20 + 1 points whose lines are all 32 bytes: coordinates k / 10000 for k in 0..99999 print as d.dddd,
+    stored BGR with blue in 10..99 and green, red in 100..255 prints as ddd ddd dd."""
+    rng = np.random.default_rng(32)
+    n = 3 * CHUNK_LINES + 1
+    xyz = rng.integers(0, 100000, (n, 3)).astype(np.float64) / 10000
+    bgr = np.empty((n, 3), np.uint8)
+    bgr[:, 0] = rng.integers(10, 100, n)
+    bgr[:, 1:] = rng.integers(100, 256, (n, 2))
+    return xyz, bgr, torch.from_numpy(xyz).cuda(), torch.from_numpy(bgr).cuda()
+
+
+@pytest.mark.parametrize("n", [CHUNK_LINES, CHUNK_LINES + 1, 3 * CHUNK_LINES, 3 * CHUNK_LINES + 1])
+def test_chunk_boundaries(tmp_path, fixed_width_cloud, n):
+    from structured_light_for_3d_model_replication_amd import ply
+    xyz, bgr, xd, bd = fixed_width_cloud
+    want = ply.ply_text(xyz[:n], bgr[:n]).encode()
+    head = want.index(b"end_header\n") + len(b"end_header\n")
+    assert len(want) - head == 32 * n   # what places the chunk boundaries
+    a, b = tmp_path / "a.ply", tmp_path / "b.ply"
+    for out in (a, b):                  # the second run meets the first one's buffer contents
+        ply.save_ply_device(xd[:n], bd[:n], str(out))
+    got_a, got_b = a.read_bytes(), b.read_bytes()
+    assert len(got_a) == len(want) and len(got_b) == len(want)
+    assert _same(got_a, got_b)
+    assert _same(got_a, want)
+
+
+def test_one_context_both_writers_and_growing_slots(tmp_path):
+    """The mesh writers and the cloud writer take turns on one context: the ring with 12 800-byte slots, a cloud,
+    the mesh writers again in larger chunks (the slots grow), the cloud again."""
+    from structured_light_for_3d_model_replication_amd import merge, mesh, ply
+    from tests import meshwrite_oracle as wo
+    P, T = wo.random_mesh(256 * 5 + 3, nv=700, seed=11)   # tests/test_gpu_meshwrite.py's ring mesh
+    Pd, Td = torch.from_numpy(np.array(P)).cuda(), torch.from_numpy(np.array(T)).cuda()
+    rng = np.random.default_rng(8)
+    xyz = rng.standard_normal((50_000, 3)) * 40
+    bgr = rng.integers(0, 256, (50_000, 3), dtype=np.uint8)
+    xd, bd = torch.from_numpy(xyz).cuda(), torch.from_numpy(bgr).cuda()
+    cloud_want = ply.ply_text(xyz, bgr).encode()
+    eng = merge._engine(None)
+    host = {}
+    for ext in (".stl", ".ply"):   # the host route (NumPy in) of the same writer
+        mesh.write_triangle_mesh(str(tmp_path / ("host" + ext)), P, T)
+        host[ext] = (tmp_path / ("host" + ext)).read_bytes()
+    assert host[".stl"] == wo.stl_bytes(P, T) and host[".ply"] == wo.mesh_ply_bytes(P, T)
+
+    def mesh_file(ext, chunk):
+        out = tmp_path / ("m" + ext)
+        mesh.write_triangle_mesh(str(out), Pd, Td, chunk_triangles=chunk)
+        return out.read_bytes()
+
+    def cloud_file():
+        out = tmp_path / "c.ply"
+        eng.write_ply(str(out), xd, bd)
+        return out.read_bytes()
+
+    assert mesh_file(".stl", 256) == host[".stl"]
+    assert _same(cloud_file(), cloud_want)
+    assert mesh_file(".stl", 512) == host[".stl"]
+    assert mesh_file(".ply", 512) == host[".ply"]
+    assert _same(cloud_file(), cloud_want)
+
+
+@pytest.mark.parametrize("kind", ["directory", "missing_parent"])
+def test_device_ply_path_that_cannot_be_opened(tmp_path, kind):
+    from structured_light_for_3d_model_replication_amd import ply
+    rng = np.random.default_rng(3)
+    xyz = rng.standard_normal((3000, 3))
+    bgr = rng.integers(0, 256, (3000, 3), dtype=np.uint8)
+    xd, bd = torch.from_numpy(xyz).cuda(), torch.from_numpy(bgr).cuda()
+    if kind == "directory":
+        bad = tmp_path / "dir.ply"
+        bad.mkdir()
+        before = ["dir.ply"]
+    else:
+        bad = tmp_path / "no" / "such" / "c.ply"
+        before = []
+    with pytest.raises(OSError):
+        ply.save_ply_device(xd, bd, str(bad))
+    assert sorted(p.name for p in tmp_path.rglob("*")) == before   # nothing was created
+    out = tmp_path / "next.ply"
+    ply.save_ply_device(xd, bd, str(out))                          # the context is fine afterwards
+    assert out.read_bytes() == ply.ply_text(xyz, bgr).encode()
+
+
+def test_libc_fallback_between_ring_writes(tmp_path):
+    rng = np.random.default_rng(6)
+    xyz = rng.standard_normal((20_000, 3)) * 10
+    bgr = rng.integers(0, 256, (20_000, 3), dtype=np.uint8)
+    nan = xyz.copy()
+    nan[4321, 2] = np.nan
+    _check(tmp_path, xyz, bgr, "ring")
+    _check(tmp_path, nan, bgr, "nan")
+    _check(tmp_path, xyz, bgr, "ring_again")
