@@ -223,7 +223,16 @@ def fill_stack(files: list[str], stack_out, tex_out, workers: int | None = None,
     left untouched and True is returned (the caller may pass no texture).
     The colour decode (the longest task: a colour JPEG's RGB decode) starts
     first, beside the gray ones.  ``on_plane(j)`` is called, on the decoding
-    thread, as soon as plane j is in ``stack_out`` (e.g. to start its upload)."""
+    thread, as soon as plane j is in ``stack_out`` (e.g. to start its upload).
+
+    When the call returns or raises, none of its tasks is running or will
+    run: nothing writes ``stack_out`` or ``tex_out`` and ``on_plane`` is not
+    called afterwards, so the caller may hand the buffers to the next call at
+    once.  On a failure (a plane's decode, the colour decode, ``on_plane``
+    raising) the tasks that have not started are cancelled and the running
+    ones, colour included, are waited for before the exception is raised: that
+    of the lowest-numbered failed plane, the colour task's only when no plane
+    failed."""
     n = len(stack_out)
     workers = default_workers() if workers is None else workers
     if len(files) < n:
@@ -250,12 +259,17 @@ def fill_stack(files: list[str], stack_out, tex_out, workers: int | None = None,
     if workers > 1 and n > 1:
         pool = _pool(workers)
         fc = pool.submit(colour)
+        fs = [pool.submit(one, j) for j in range(n)]
         try:
-            list(pool.map(one, range(n)))
+            for f in fs:  # in plane order: the first to raise is the lowest failed plane
+                f.result()
+            return fc.result()
         except BaseException:
-            fc.exception()  # waited for: nothing writes tex_out after the call returns
+            # the pool is shared and outlives the call: drop what has not started, wait for
+            # what has -- nothing of this call touches the buffers after it has raised
+            from concurrent.futures import wait
+            wait([f for f in (fc, *fs) if not f.cancel()])
             raise
-        return fc.result()
     for j in range(n):
         one(j)
     return colour()

@@ -102,7 +102,13 @@ def _decode_device(folder, calib, n_cols, n_rows, mask_mode, device, xyz_dtype, 
         def upload(j):  # each plane's H2D starts on the decoding thread as soon as the plane is in place
             with torch.cuda.stream(s):
                 ds[j].copy_(hs[j], non_blocking=True)
-        gray_tex = io.fill_stack(files, hs.numpy(), ht.numpy(), on_plane=upload)
+        try:
+            gray_tex = io.fill_stack(files, hs.numpy(), ht.numpy(), on_plane=upload)
+        except BaseException:
+            # fill_stack has stopped its tasks; the uploads they queued are waited for here, so
+            # none reads hs while the next caller, once the lock is free, writes it
+            s.synchronize()
+            raise
         if not gray_tex:
             dt.copy_(ht, non_blocking=True)
         res = eng.decode_triangulate(ds, n_cols, n_rows, texture=None if gray_tex else dt, mask_mode=mask_mode,
