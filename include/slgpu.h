@@ -706,6 +706,41 @@ int sl_write_mesh_ply_colors_device(sl_ctx* ctx, const char* path, const double*
                                     const int32_t* triangles, int64_t n_triangles, const uint8_t* bgr,
                                     int64_t chunk_triangles, void* stream);
 
+/* ---- mesh smoothing (csrc/slmeshsmooth.inl, which states the definitions) ----
+ * Open3D's compute_adjacency_list / filter_smooth_simple / filter_smooth_laplacian
+ * / filter_smooth_taubin for the vertices, restated order-free (parity with
+ * Open3D is unpinned; exact against tests/meshsmooth_oracle.py).  vertices f64
+ * [n_vertices][3], triangles int32 [n_triangles][3] (device); n_vertices < 2^31,
+ * 6 n_triangles < 2^32.  A pass of its own reads every index first: one outside
+ * 0 .. n_vertices - 1 is SL_EINDEX and nothing is indexed.  Zero triangles /
+ * vertices succeed.  Blocking on `stream`; scratch from the merge stage's pool.
+ *   sl_mesh_adjacency   N(v): the indices that share a triangle with v ((a, a, b)
+ *       puts a into its own set), as CSR: row_start int64 [n_vertices + 1],
+ *       neighbours int32 [capacity 6 n_triangles], every row ascending without
+ *       duplicates, the entry count -> *n_neighbours.  boundary u8 [n_vertices]
+ *       (may be NULL): 1 for a vertex with an edge {v, w}, w != v, that is the
+ *       side of exactly one (triangle, side) pair.
+ *   sl_mesh_smooth      method 0 simple: p' = (p + the neighbours in ascending
+ *       index) / (1 + |N|); 1 laplacian: `iterations` steps p' = p + lambda (sum_j
+ *       w_j p_j / sum_j w_j - p), w_j = 1 / (|p - p_j| + 1e-12), folded in
+ *       ascending neighbour index; 2 taubin: a lambda step then a mu step per
+ *       iteration.  Every step reads the previous step's positions; iterations
+ *       0 copies.  A vertex with an empty row keeps its position; with
+ *       fixed_boundary != 0 so does every boundary vertex.  -> out_vertices f64
+ *       [n_vertices][3], which must not overlap `vertices`.  A non-finite vertex,
+ *       negative iterations, a non-finite lambda (methods 1, 2) or mu (method 2),
+ *       another method: SL_EINVAL.
+ *   sl_mesh_smooth_stats   the calling thread's last call of either: host
+ *       milliseconds per stage (keys, sort, CSR, iterations; stage_ms[capacity],
+ *       zero-filled) -- a measurement aid. */
+int sl_mesh_adjacency(sl_ctx* ctx, const int32_t* triangles, int64_t n_triangles, int64_t n_vertices,
+                      int64_t* row_start, int32_t* neighbours, uint8_t* boundary, int64_t* n_neighbours,
+                      void* stream);
+int sl_mesh_smooth(sl_ctx* ctx, const double* vertices, int64_t n_vertices, const int32_t* triangles,
+                   int64_t n_triangles, int method, int iterations, double lambda, double mu, int fixed_boundary,
+                   double* out_vertices, void* stream);
+int sl_mesh_smooth_stats(double* stage_ms, int capacity);
+
 /* ---- consistent tangent-plane normal orientation (processing.py:201, :282) ----
  * orient_normals_consistent_tangent_plane restated on the kNN graph alone
  * (csrc/slorient.inl; tests/orient_oracle.py is the CPU restatement, bit for

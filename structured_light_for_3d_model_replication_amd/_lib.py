@@ -56,6 +56,7 @@ EXPORTS = ("sl_abi_version", "sl_ctx_create", "sl_ctx_destroy", "sl_ctx_last_err
            "sl_mesh_triangle_normals", "sl_mesh_vertex_normals", "sl_write_stl_device", "sl_write_mesh_ply_device",
            "sl_mesh_write_stats",
            "sl_mesh_transfer_colors", "sl_mesh_transfer_colors_stats", "sl_write_mesh_ply_colors_device",
+           "sl_mesh_adjacency", "sl_mesh_smooth", "sl_mesh_smooth_stats",
            "sl_information_matrix", "sl_pose_graph_optimize",
            "sl_radius_count", "sl_cluster_dbscan", "sl_cluster_dbscan_stats", "sl_nearest_neighbor_distance",
            "sl_ball_pivot_max_neighbours", "sl_ball_pivot_candidates", "sl_ball_pivot_candidates_stats",
@@ -145,6 +146,10 @@ _SIGS = {
                                        ctypes.POINTER(ctypes.c_uint8), _vp, _vp, _vp]),
     "sl_mesh_transfer_colors_stats": (_i32, [ctypes.POINTER(ctypes.c_double), _i32]),
     "sl_write_mesh_ply_colors_device": (_i32, [_vp, ctypes.c_char_p, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
+    "sl_mesh_adjacency": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, ctypes.POINTER(_i64), _vp]),
+    "sl_mesh_smooth": (_i32, [_vp, _vp, _i64, _vp, _i64, _i32, _i32, ctypes.c_double, ctypes.c_double, _i32, _vp,
+                              _vp]),
+    "sl_mesh_smooth_stats": (_i32, [ctypes.POINTER(ctypes.c_double), _i32]),
     "sl_orient_normals_mst": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, ctypes.POINTER(_i64),
                                      ctypes.POINTER(_i64), _vp]),
     "sl_orient_normals_mst_stats": (_i32, [ctypes.POINTER(_i32), ctypes.POINTER(_i32), _i32]),

@@ -2297,3 +2297,5 @@ int sl_merge_pool_poison(int byte, int64_t* poisoned_bytes) {
 #include "slmeshwrite.inl"
 // vertex colours: cloud-to-mesh transfer by tiers of nearest samples, the coloured PLY vertex record
 #include "slmeshcolor.inl"
+// mesh smoothing: the vertex adjacency list (CSR), the simple, Laplacian and Taubin filters
+#include "slmeshsmooth.inl"

@@ -46,6 +46,13 @@ an inverse-squared-distance blend (csrc/slmeshcolor.inl states the definition;
 exact against tests/meshcolor_oracle.py) -- and ``write_triangle_mesh(...,
 colors=...)`` writes them as ``uchar red green blue`` in the ``.ply``.
 
+``filter_smooth_taubin``, ``filter_smooth_laplacian`` and ``filter_smooth_simple``
+move the vertices: Open3D's calls of those names on ``adjacency_list``'s CSR
+(the sorted sides of the triangles and their transpose), one thread per vertex folding its
+neighbours in ascending index (csrc/slmeshsmooth.inl states the rules; exact
+against tests/meshsmooth_oracle.py).  The drop-ins apply them when asked to
+(``smooth_iterations``, ``smooth_method``, ``smooth_fixed_boundary``).
+
 Open3D's Poisson is the adaptive-octree variant and is not installed here:
 parity with Open3D is unpinned, and tests/mesh_oracle.py is the CPU restatement
 the tests check against -- bit for bit for every stage except the solve.
@@ -463,6 +470,95 @@ def simplify_vertex_clustering(vertices, triangles, voxel_size: float, *, device
     _call(eng, "sl_mesh_simplify_clustering", _ptr(Vx) if len(Vx) else None, len(Vx), _ptr(T) if len(T) else None,
           len(T), float(voxel_size), _ptr(ov), _ptr(ot), ctypes.byref(nv), ctypes.byref(nt))
     return ov[: nv.value], ot[: nt.value]
+
+
+def adjacency_list(triangles, n_vertices, *, boundary: bool = False, device=None):
+    """TriangleMesh.compute_adjacency_list as CSR -> (row_start int64 [V + 1],
+    neighbours int32 [M][, boundary bool [V]]) on the device: row v, the indices
+    that share a triangle with v, is ``neighbours[row_start[v]:row_start[v + 1]]``,
+    ascending without duplicates; a vertex of no triangle has an empty row.  As
+    in Open3D's inserts a triangle that repeats an index puts the vertex into its
+    own set: (a, a, b) gives N(a) = {a, b}.  ``boundary``: also the vertices with
+    an edge {v, w}, w != v, that is the side of exactly one triangle
+    (csrc/slmeshsmooth.inl states the rules, tests/meshsmooth_oracle.py is their
+    CPU form, which the result equals exactly).  An index outside 0 .. V - 1
+    raises IndexError."""
+    eng = _engine(device)
+    T = _tris(triangles, eng.device)
+    nv, t = int(n_vertices), len(T)
+    if not 0 <= nv < 2 ** 31:
+        raise ValueError("n_vertices must be in 0 .. 2^31 - 1")
+    rows = torch.empty(nv + 1, dtype=torch.int64, device=eng.device)
+    nb = torch.empty(max(6 * t, 1), dtype=torch.int32, device=eng.device)
+    bnd = torch.empty(max(nv, 1), dtype=torch.uint8, device=eng.device) if boundary else None
+    m = ctypes.c_int64()
+    _call(eng, "sl_mesh_adjacency", _ptr(T) if t else None, t, nv, _ptr(rows), _ptr(nb), _ptr(bnd), ctypes.byref(m))
+    nb = nb[: m.value].clone()  # (not a view of the 6 T capacity)
+    return (rows, nb, bnd[:nv].bool()) if boundary else (rows, nb)
+
+
+_SMOOTH_METHODS = {"simple": 0, "laplacian": 1, "taubin": 2}
+
+
+def _smooth(method, vertices, triangles, iterations, lam, mu, fixed_boundary, device):
+    eng, V, T = _mesh_args(vertices, triangles, device)
+    if int(iterations) != iterations or iterations < 0:
+        raise ValueError("iterations must be a non-negative integer")
+    if not (np.isfinite(lam) and np.isfinite(mu)):
+        raise ValueError("lambda_filter and mu must be finite")
+    out = torch.empty((max(len(V), 1), 3), dtype=torch.float64, device=eng.device)
+    _call(eng, "sl_mesh_smooth", _ptr(V) if len(V) else None, len(V), _ptr(T) if len(T) else None, len(T),
+          _SMOOTH_METHODS[method], int(iterations), float(lam), float(mu), int(bool(fixed_boundary)), _ptr(out))
+    return out[: len(V)]
+
+
+def filter_smooth_simple(vertices, triangles, iterations: int = 1, *, fixed_boundary: bool = False, device=None):
+    """TriangleMesh.filter_smooth_simple -> the new vertices f64 [V, 3] on the
+    device (the triangles are untouched): per iteration and axis, p' = (p + the
+    neighbours' p in ascending index) / (1 + |N(v)|), every step from the previous
+    step's positions; ``iterations = 0`` returns a copy.  Deviations: Open3D
+    walks an unordered_set, so its last bits depend on the hash order, here the
+    sum runs in ascending neighbour index (``adjacency_list``'s rows); with
+    ``fixed_boundary`` (an extension; off is Open3D's behaviour) the boundary
+    vertices keep their position in every step and their neighbours still read
+    them.  Only the vertices are filtered, not normals or colours.  Exact against
+    tests/meshsmooth_oracle.py (csrc/slmeshsmooth.inl states the rules).  A
+    non-finite vertex or negative ``iterations`` raises ValueError, an index
+    outside 0 .. V - 1 IndexError."""
+    return _smooth("simple", vertices, triangles, iterations, 0.0, 0.0, fixed_boundary, device)
+
+
+def filter_smooth_laplacian(vertices, triangles, iterations: int = 1, lambda_filter: float = 0.5, *,
+                            fixed_boundary: bool = False, device=None):
+    """TriangleMesh.filter_smooth_laplacian -> the new vertices f64 [V, 3] on the
+    device: ``iterations`` steps p' = p + lambda (sum_j w_j p_j / sum_j w_j - p)
+    with w_j = 1 / (|p - p_j| + 1e-12) over the neighbours in ascending index,
+    every step from the previous step's positions.  Deviations: the fold order
+    (Open3D: the order of an unordered_set); a vertex of no triangle keeps its
+    position (Open3D divides 0 / 0); ``fixed_boundary`` as in
+    ``filter_smooth_simple``.  A non-finite vertex or ``lambda_filter`` or
+    negative ``iterations`` raises ValueError, an index outside 0 .. V - 1
+    IndexError."""
+    return _smooth("laplacian", vertices, triangles, iterations, lambda_filter, 0.0, fixed_boundary, device)
+
+
+def filter_smooth_taubin(vertices, triangles, iterations: int = 1, lambda_filter: float = 0.5, mu: float = -0.53, *,
+                         fixed_boundary: bool = False, device=None):
+    """TriangleMesh.filter_smooth_taubin -> the new vertices f64 [V, 3] on the
+    device: per iteration ``filter_smooth_laplacian``'s step with factor
+    ``lambda_filter`` and then with ``mu`` (negative: it undoes the shrinkage of
+    the first), 2 x iterations launches.  The same deviations and errors; ``mu``
+    must be finite too."""
+    return _smooth("taubin", vertices, triangles, iterations, lambda_filter, mu, fixed_boundary, device)
+
+
+def smooth_stats(*, device=None) -> dict:
+    """Host milliseconds per stage of this thread's last ``adjacency_list`` or
+    ``filter_smooth_*`` (sl_mesh_smooth_stats; a measurement aid)."""
+    eng = _engine(device)
+    v = (ctypes.c_double * 4)()
+    _lib.check(eng._L.sl_mesh_smooth_stats(v, 4), None, "sl_mesh_smooth_stats")
+    return {"keys_ms": v[0], "sort_ms": v[1], "csr_ms": v[2], "iterations_ms": v[3]}
 
 
 def quantile(values, q: float) -> float:

@@ -51,6 +51,12 @@ errors, and runs them on the GPU through ``merge`` (libslgpu.so):
   used and the number filled; an ``.stl`` output or an input without colour properties prints a note and is
   written as without it.  Deviations: Open3D's Poisson colours come from its octree's data field, and after
   ``simplify_voxel_size`` it averages the members' colours where this takes the transfer at the vertex.
+  Three more, ``smooth_iterations=None``, ``smooth_method="taubin"`` ("taubin", "laplacian" or "simple";
+  anything else raises ValueError) and ``smooth_fixed_boundary=False``, smooth the vertices
+  (``mesh.filter_smooth_taubin`` / ``_laplacian`` / ``_simple`` with their default factors,
+  csrc/slmeshsmooth.inl) after the clean-up and before the colours and the writer, with one line of the
+  method, the iterations and the vertex count; without ``smooth_iterations`` nothing changes.  Deviations:
+  a vertex's neighbours are summed in ascending index (Open3D: the order of an unordered_set).
 
 Without Open3D, "a point cloud object" is a ``Cloud(points, colors)`` of
 device tensors (f64 [N, 3], BGR u8 [N, 3] or None).  It is accepted wherever
@@ -230,12 +236,34 @@ class ProcessingLogic:
             print(f"[{tag}] Vertex clustering (voxel_size={simplify_voxel_size}): {before} -> {len(T)} triangles")
         return V, T
 
+    _SMOOTH_FILTERS = {"taubin": mesh.filter_smooth_taubin, "laplacian": mesh.filter_smooth_laplacian,
+                       "simple": mesh.filter_smooth_simple}
+
+    @staticmethod
+    def _check_smooth_method(smooth_method):
+        """Before anything is loaded: a method that is none of the three raises ValueError."""
+        if smooth_method not in ProcessingLogic._SMOOTH_FILTERS:
+            raise ValueError(f"Unknown smooth_method: {smooth_method} (taubin, laplacian or simple)")
+
+    @staticmethod
+    def _smooth_mesh(tag, V, T, smooth_iterations, smooth_method, smooth_fixed_boundary):
+        """The opt-in smoothing of the drop-ins' mesh (mesh.filter_smooth_taubin / _laplacian / _simple with their
+        default factors) -> the vertices that are written; ``smooth_iterations`` None: untouched."""
+        if smooth_iterations is None:
+            return V
+        V = ProcessingLogic._SMOOTH_FILTERS[smooth_method](V, T, int(smooth_iterations),
+                                                           fixed_boundary=bool(smooth_fixed_boundary), device=V.device)
+        print(f"[{tag}] Smoothing ({smooth_method}, {int(smooth_iterations)} iterations): {len(V)} vertices")
+        return V
+
     @staticmethod
     def reconstruct_stl(input_path, output_path, mode="watertight", params=None, *, budget_bytes=None,
                         tangent_planes=None, ball_pivoting=False, keep_largest_component=False,
-                        min_component_triangles=None, simplify_voxel_size=None, vertex_colors=False):
+                        min_component_triangles=None, simplify_voxel_size=None, vertex_colors=False,
+                        smooth_iterations=None, smooth_method="taubin", smooth_fixed_boundary=False):
         if not os.path.exists(input_path):
             raise FileNotFoundError(f"Input file not found: {input_path}")
+        ProcessingLogic._check_smooth_method(smooth_method)
         params = {} if params is None else params
         print(f"[Recon] Loading {input_path}...")
         P, N, C = ProcessingLogic._load_colored_for_meshing(input_path)
@@ -279,6 +307,7 @@ class ProcessingLogic:
                                            simplify_voxel_size)
         if len(V) == 0:
             raise ValueError("Generated mesh is empty.")
+        V = ProcessingLogic._smooth_mesh("Recon", V, T, smooth_iterations, smooth_method, smooth_fixed_boundary)
         colors = ProcessingLogic._vertex_colors("Recon", output_path, P, C, V, avg_dist) if vertex_colors else None
         print("[Recon] Computing normals and saving...")
         mesh.write_triangle_mesh(output_path, V, T, colors=colors)
@@ -287,9 +316,11 @@ class ProcessingLogic:
     @staticmethod
     def mesh_360(input_path, output_path, depth=10, density_trim=0.01, orientation_mode="tangent", *,
                  budget_bytes=None, tangent_planes=None, keep_largest_component=False, min_component_triangles=None,
-                 simplify_voxel_size=None, vertex_colors=False):
+                 simplify_voxel_size=None, vertex_colors=False, smooth_iterations=None, smooth_method="taubin",
+                 smooth_fixed_boundary=False):
         if not os.path.exists(input_path):
             raise FileNotFoundError(f"Input file not found: {input_path}")
+        ProcessingLogic._check_smooth_method(smooth_method)
         print(f"[360 Mesh] Loading {input_path}...")
         P, _, C = ProcessingLogic._load_colored_for_meshing(input_path)
         print("[360 Mesh] Estimating normals...")
@@ -326,6 +357,7 @@ class ProcessingLogic:
             print("[360 Mesh] Density trim is 0.0 -> Keeping watertight result.")
         V, T = ProcessingLogic._clean_mesh("360 Mesh", V, T, keep_largest_component, min_component_triangles,
                                            simplify_voxel_size)
+        V = ProcessingLogic._smooth_mesh("360 Mesh", V, T, smooth_iterations, smooth_method, smooth_fixed_boundary)
         colors = ProcessingLogic._vertex_colors("360 Mesh", output_path, P, C, V) if vertex_colors else None
         mesh.write_triangle_mesh(output_path, V, T, colors=colors)
         print(f"[360 Mesh] Saved to {output_path}")
