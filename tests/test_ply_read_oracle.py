@@ -32,7 +32,10 @@ def _table(case, res):
 
 
 def _split_file(path):
-    data = open(path, "rb").read()
+    return _split_bytes(open(path, "rb").read())
+
+
+def _split_bytes(data):
     end = data.find(b"end_header\n")
     head = data[:end].decode("ascii").split("\n")
     n = next(int(line.split()[2]) for line in head if line.startswith("element vertex"))
@@ -63,6 +66,10 @@ def test_accepted_case_equals_host_reader(case, tmp_path):
     assert res["undecided"] == case.undecided
     if case.tiers:
         assert res["tiers"] == case.tiers
+    _table_is_the_host_readers(case, res, tmp_path)
+
+
+def _table_is_the_host_readers(case, res, tmp_path):
     T = _table(case, res)
     f = _write(tmp_path, case)
     P, C = ply.read_ply(f)
@@ -149,3 +156,275 @@ def test_binary_odd_offsets_file_is_readable_by_the_host(tmp_path):
     open(f, "wb").write(cases.binary_odd_file())
     P, C = ply.read_ply(f)
     assert P.shape == (257, 3) and C.shape == (257, 3) and ply.read_normals(f).shape == (257, 3)
+
+
+# =====================================================================
+# The preconditions of tests/test_gpu_ply_read_paths.py, case by case.
+# =====================================================================
+def _accepted(case, tmp_path, undecided=0):
+    res = oracle.parse_body(case.body, case.n, len(case.props), case.colour_cols, case.cap)
+    assert res["status"] == oracle.ACCEPTED == case.status
+    assert res["undecided"] == undecided == case.undecided
+    _table_is_the_host_readers(case, res, tmp_path)
+    return res
+
+
+def _put(tmp_path, name, data):
+    f = str(tmp_path / f"{name}.ply")
+    with open(f, "wb") as fh:
+        fh.write(data)
+    return f
+
+
+# ---- 1: beyond one scan pass ----
+@pytest.mark.parametrize("nb,rows,per", [(1024, 65536, 1), (1025, 65552, 2)])
+def test_dense_bodies_fill_the_scan(nb, rows, per, tmp_path):
+    case = cases.dense_case(nb)
+    assert case.n == rows and len(case.body) == 64 * rows
+    assert cases.n_chunks(case.body) == nb and cases.scan_per(case.body) == per
+    assert all(case.body[i] == 10 for i in range(63, len(case.body) - 64, 64))  # 64-byte lines
+    empty = [t for t in range(cases.SCAN_THREADS) if t * per >= nb]  # k_ply_scan: lo = tid * per >= nb
+    if nb == 1024:
+        assert len(case.body) == 1024 * cases.CHUNK and not empty
+        assert case.body[-1:].isdigit() and b"\n" not in case.body[-64:]  # the last token ends body and chunk
+    else:
+        assert len(case.body) == 4195328 and empty == list(range(513, 1024))
+    _accepted(case, tmp_path)
+
+
+def test_sparse_body_has_mostly_empty_chunks(tmp_path):
+    case = cases.sparse_case()
+    nb = cases.n_chunks(case.body)
+    assert case.n == 700 and nb >= 1025 and cases.scan_per(case.body) == 2
+    with_start = {m.start() // cases.CHUNK for m in oracle._SPLIT.finditer(case.body)}
+    assert nb - len(with_start) >= 300  # a row's tokens start in one chunk or two: hundreds hold none
+    assert b" " * 5999 + b"\t\n" in case.body and b" " * 6000 + b"\n" in case.body
+    _accepted(case, tmp_path)
+
+
+# ---- 2: RUN_MAX, both sides ----
+@pytest.mark.parametrize("blanks", [oracle.RUN_MAX, oracle.RUN_MAX + 1])
+@pytest.mark.parametrize("shape", cases.RUN_SHAPES)
+def test_run_of_blanks_before_a_token(shape, blanks, tmp_path):
+    case = cases.run_case(shape, blanks)
+    assert oracle.RUN_MAX == 65536
+    start, length = cases.blank_run(case.body)
+    assert length == blanks and set(case.body[start:start + length]) == set(b" \t")
+    assert (start + length) // cases.CHUNK - start // cases.CHUNK >= 16  # the run crosses 16 chunk edges by itself
+    toks = [m.start() for m in oracle._SPLIT.finditer(case.body)]
+    k = toks.index(start + length)  # the token behind the run
+    before = case.body[start - 1:start]
+    assert (k, before) == {"after_break": (3, b"\n"), "body_start": (0, b""), "inside_row": (4, b"0")}[shape]
+    res = oracle.parse_body(case.body, case.n, 3)
+    assert res["status"] == case.status == (oracle.ACCEPTED if blanks == oracle.RUN_MAX else oracle.RAGGED_LINE)
+    P, _ = ply.read_ply(_write(tmp_path, case))  # np.loadtxt reads both
+    np.testing.assert_array_equal(_bits(P), _bits(np.array([float(t) for t in case.body.split()]).reshape(3, 3)))
+    if blanks == oracle.RUN_MAX:
+        _table_is_the_host_readers(case, res, tmp_path)
+
+
+# ---- 3: undecided tokens and the host's runs ----
+def test_undecided_runs_layout(tmp_path):
+    case = cases.undecided_runs_case()
+    spans = cases.undecided_spans(case.body)
+    assert len(spans) == 7
+    assert spans[0][0] == 0 and sum(spans[-1]) == len(case.body)  # the body's first token and its last
+    runs = cases.host_runs(spans)
+    assert [len(r) for r in runs] == [2, 1, 1, 1, 1, 1]
+    (o0, l0), (o1, _) = runs[0]
+    assert 0 < o1 - (o0 + l0) < cases.GAP  # one run: less than GAP apart
+    ends = [r[-1][0] + r[-1][1] for r in runs]
+    assert all(runs[i + 1][0][0] - ends[i] >= cases.GAP for i in range(len(runs) - 1))  # GAP or more: a new run
+    assert sum(o // cases.CHUNK != (o + n - 1) // cases.CHUNK for o, n in spans) == 1  # one across a chunk edge
+    firsts = [i for i, (p, t) in enumerate((m.start(), m.group()) for m in oracle._SPLIT.finditer(case.body))
+              if oracle.tier(t) == "undecided"]
+    assert all(b - a > 3 for a, b in zip(firsts[1:], firsts[2:]))  # decided rows between the later ones
+    _accepted(case, tmp_path, undecided=7)
+
+
+def test_undecided_span_limit_layout(tmp_path):
+    """Structure only (no parse_body over 17 MB): the row pitch keeps every
+    gap under GAP, so the runs end where SPAN says and nowhere else."""
+    case = cases.undecided_span_case()
+    body = case.body
+    assert len(body) == 4300 * 4000 and body.count(b"\n") == 4300
+    assert all(body[i] == 10 for i in range(3999, len(body), 4000))
+    assert set(body) <= oracle.ALPHABET
+    spans = cases.undecided_spans(body)
+    assert len(spans) == case.undecided == 4300 and [o for o, _ in spans] == list(range(0, len(body), 4000))
+    assert all(body[o:o + n] == b"%de23" % k for k, (o, n) in enumerate(spans))
+    gaps = [spans[i + 1][0] - sum(spans[i]) for i in range(4299)]
+    assert 3990 <= min(gaps) and max(gaps) == 3996 < cases.GAP
+    runs = cases.host_runs(spans)
+    first = (cases.SPAN - 8) // 4000 + 1  # tokens k with 4000 k + len("{k}e23") < 2^24; len is 7 there
+    assert [len(r) for r in runs] == [first, 4300 - first] and first == 4195
+    assert sum(runs[0][-1]) - runs[0][0][0] < cases.SPAN <= sum(runs[1][0]) - runs[0][0][0]
+    P, _ = ply.read_ply(_write(tmp_path, case))
+    np.testing.assert_array_equal(_bits(P[:, 0]), _bits([float(f"{k}e23") for k in range(4300)]))
+    assert (P[:, 1:] == [2.0, 3.0]).all()
+
+
+def test_undecided_capacity_preconditions():
+    case = cases.undecided_runs_case()
+    parse = lambda c, cap: oracle.parse_body(c.body, c.n, len(c.props), c.colour_cols, cap)  # noqa: E731
+    assert parse(case, case.undecided)["status"] == oracle.ACCEPTED
+    assert parse(case, case.undecided - 1)["status"] == oracle.UNDECIDED_OVERFLOW
+    plain = cases.shape_cases_by_name()["rows257_cols6"]
+    res = parse(plain, 0)
+    assert res["status"] == oracle.ACCEPTED and res["undecided"] == 0
+
+
+# ---- 4: the files of the stream and context tests ----
+def test_stream_sequence_files(tmp_path):
+    P, C = ply.read_ply(_put(tmp_path, "one", cases.one_row_file()))
+    assert P.tolist() == [[1.5, -2.25, 3.125]] and C.tolist() == [[30, 20, 10]]
+    for n in (3, 300000):
+        X, _ = cases.write_cloud(n, n)
+        assert X.shape == (n, 3) and np.abs(X).max() < 9e11  # the device formatter takes every point
+
+
+# ---- 5: binary values ----
+def test_widen_f32_bits_is_the_conversion():
+    u = np.random.default_rng(1).integers(0, 2 ** 32, 20000, dtype=np.uint64).astype(np.uint32)
+    u = np.concatenate([u, np.array(cases.F32_SPECIALS, dtype=np.uint32), np.arange(1, 300, dtype=np.uint32)])
+    u = u[~np.isnan(u.view(np.float32)) | ((u & 0x00400000) != 0)]  # a signalling NaN is quieted: not this table's
+    want = np.array([cases.widen_f32_bits(int(v)) for v in u], dtype=np.uint64)
+    np.testing.assert_array_equal(u.view(np.float32).astype(np.float64).view(np.uint64), want)
+
+
+@pytest.mark.parametrize("kind", ["float", "double"])
+def test_binary_specials_keep_their_bits_on_the_host(kind, tmp_path):
+    f = _put(tmp_path, "specials", cases.binary_specials_file(kind))
+    bits = cases.specials_bits(kind)
+    if kind == "float":
+        assert all((b >> 22) & 1 for b in cases.F32_SPECIALS if (b & 0x7FFFFFFF) > 0x7F800000)  # quiet NaNs only
+        want = np.array([[cases.widen_f32_bits(int(v)) for v in row] for row in bits], dtype=np.uint64)
+    else:
+        assert all((b >> 51) & 1 for b in cases.F64_SPECIALS if (b & (2 ** 63 - 1)) > 0x7FF << 52)
+        want = bits
+    P, _ = ply.read_ply(f)
+    N = ply.read_normals(f)
+    got = np.concatenate([P, N], 1).view(np.uint64)
+    np.testing.assert_array_equal(got, want)
+    for j in range(6):  # every special in every column, no two of them the same f64
+        assert len(set(got[:, j].tolist())) == 16
+    if kind == "float":
+        assert P[2, 0] == 2.0 ** -149 and P[4, 0] == 2.0 ** -126 - 2.0 ** -149 and P[6, 0] == 2.0 ** -126
+        assert P[3, 0] == -2.0 ** -149 and np.signbit(P[1, 0]) and P[1, 0] == 0
+    else:
+        assert P[2, 0] == 5e-324 and P[8, 0] == np.finfo(np.float64).max
+    assert np.isnan(P[12:, 0]).all() and np.isinf(P[10:12, 0]).all()
+
+
+@pytest.mark.parametrize("n", cases.INT_ROWS)
+@pytest.mark.parametrize("type_name", cases.INT_TYPES)
+def test_binary_int_extremes_on_the_host(type_name, n, tmp_path):
+    data, V = cases.int_extremes(type_name, n)
+    info = np.iinfo(np.dtype(ply._PLY_TYPES[type_name]))
+    assert V.shape == (n, 4) and info.min in V[:, :3] and info.max in V[:, :3]
+    assert sorted(V[-1].tolist()) == sorted([info.min, info.max] * 2)  # the last element of the table is an extreme
+    P, _ = ply.read_ply(_put(tmp_path, "ints", data))
+    assert P.dtype == np.float64
+    np.testing.assert_array_equal(P, V[:, :3].astype(np.float64))
+    assert (P.astype(np.int64) == V[:, :3]).all()
+
+
+def test_int_types_are_all_of_them():
+    assert len(cases.INT_TYPES) == 12 and len({ply._PLY_TYPES[t] for t in cases.INT_TYPES}) == 6
+    assert [4 * n for n in cases.INT_ROWS] == [4, 256, 260]  # k_plyr_unpack: 256 table elements per workgroup
+
+
+def test_binary_bodies_of_the_wrong_length(tmp_path):
+    short = _put(tmp_path, "short", cases.binary_plain_file(delta=-1))
+    long_ = _put(tmp_path, "long", cases.binary_plain_file(delta=7))
+    exact = _put(tmp_path, "exact", cases.binary_plain_file())
+    assert os.path.getsize(short) + 1 == os.path.getsize(exact) == os.path.getsize(long_) - 7
+    with pytest.raises(ValueError):
+        ply.read_ply(short)
+    P, C = ply.read_ply(long_)
+    Pe, Ce = ply.read_ply(exact)
+    assert P.shape == (5, 3)
+    np.testing.assert_array_equal(_bits(P), _bits(Pe))
+    np.testing.assert_array_equal(C, Ce)
+    with pytest.raises(ValueError):  # np.dtype refuses a name given twice
+        ply.read_ply(_put(tmp_path, "twice", cases.binary_x_twice_file()))
+
+
+# ---- 6: header and column routes ----
+@pytest.mark.parametrize("fmt", ["ascii", "binary_little_endian"])
+def test_long_header_lies_past_the_first_probe(fmt, tmp_path):
+    data = cases.long_header_file(fmt)
+    assert data.find(b"end_header\n") > ply._HEAD_PROBE + 3000
+    kind, n, props, body = _split_bytes(data)
+    assert (kind, n, len(props)) == (fmt, 257, 6)
+    P, C = ply.read_ply(_put(tmp_path, "long_header", data))
+    assert P.shape == (257, 3) and C.any()
+    if fmt == "ascii":
+        assert oracle.parse_body(body, n, 6, [3, 4, 5])["status"] == oracle.ACCEPTED
+    else:
+        assert len(body) == 257 * 15
+
+
+@pytest.mark.parametrize("fmt", ["ascii", "binary_little_endian"])
+def test_scattered_columns_have_no_neighbouring_triple(fmt, tmp_path):
+    data = cases.scattered_file(fmt)
+    kind, n, names, body = _split_bytes(data)
+    assert names == cases.SCATTERED and kind == fmt
+    for triple in (("x", "y", "z"), ("nx", "ny", "nz"), ("blue", "green", "red")):
+        i = [names.index(c) for c in triple]
+        assert not (i[1] == i[0] + 1 and i[2] == i[0] + 2)  # take()'s fancy-index branch
+    f = _put(tmp_path, "scattered", data)
+    P, C = ply.read_ply(f)
+    N = ply.read_normals(f)
+    assert P.shape == N.shape == C.shape == (n, 3)
+    if fmt == "ascii":
+        res = oracle.parse_body(body, n, 9, [6, 7, 8])
+        assert res["status"] == oracle.ACCEPTED
+        T = np.array(res["values"]).reshape(n, 9)
+        np.testing.assert_array_equal(_bits(T[:, [0, 2, 4]]), _bits(P))
+        np.testing.assert_array_equal(_bits(T[:, [1, 3, 5]]), _bits(N))
+        np.testing.assert_array_equal(T[:, [6, 8, 7]].astype(np.uint8), C)
+
+
+def test_ascii_x_given_twice_is_the_last_column(tmp_path):
+    case = cases.x_twice_case()
+    assert [p for _, p in case.props] == ["x", "y", "z", "x"]
+    res = oracle.parse_body(case.body, case.n, 4)
+    assert res["status"] == oracle.ACCEPTED
+    T = _table(case, res)
+    P, _ = ply.read_ply(_write(tmp_path, case))
+    np.testing.assert_array_equal(_bits(P), _bits(T[:, [3, 1, 2]]))
+    assert (T[:, 0] != T[:, 3]).all()
+
+
+@pytest.mark.filterwarnings("ignore:loadtxt. input contained no data")
+def test_vertex_count_against_the_body(tmp_path):
+    _, n, _, body = _split_bytes(cases.n0_two_rows_file())
+    assert n == 0 and oracle.parse_body(body, 0, 3)["status"] == oracle.TOKEN_COUNT
+    P, C = ply.read_ply(_put(tmp_path, "n0", cases.n0_two_rows_file()))
+    assert P.shape == (0, 3) and C.shape == (0, 3)
+    _, n, _, body = _split_bytes(cases.n2_empty_file())
+    assert n == 2 and body == b"" and oracle.parse_body(body, 2, 3)["status"] == oracle.TOKEN_COUNT
+    with pytest.raises(IndexError):  # loadtxt's empty table has no column 1
+        ply.read_ply(_put(tmp_path, "n2", cases.n2_empty_file()))
+    with pytest.raises(ValueError):
+        ply.read_ply(_put(tmp_path, "face", cases.face_element_file()))
+
+
+# ---- 7: ends and starts ----
+def test_end_cases_end_where_they_claim(tmp_path):
+    by = {c.name: c for c in cases.end_cases()}
+    assert sorted(by) == ["cr_only", "flush_16", "flush_4096_3.1250", "flush_4097_0.12345", "flush_4097_7"]
+    assert [len(by[k].body) for k in ("flush_16", "flush_4096_3.1250", "flush_4097_7", "flush_4097_0.12345")] == \
+        [16, 4096, 4097, 4097]
+    for k, c in by.items():
+        if k != "cr_only":
+            assert c.body[-1:].isdigit()  # no final line break: the last token ends on the last byte
+    one = by["flush_4097_7"].body
+    assert one[4095:] == b" 7" and one[4090:4096].isspace()  # the last chunk's only byte starts a token
+    tail = by["flush_4097_0.12345"].body
+    assert tail[4089:] == b" 0.12345"  # ... is the tail of a token that started in the chunk before
+    cr = by["cr_only"].body
+    assert b"\n" not in cr and cr.count(b"\r") == 257 and cr.endswith(b"\r")
+    for c in by.values():
+        _accepted(c, tmp_path)
