@@ -670,7 +670,8 @@ int sl_write_mesh_ply_device(sl_ctx* ctx, const char* path, const double* vertic
                              const int32_t* triangles, int64_t n_triangles, int64_t chunk_triangles, void* stream);
 int sl_mesh_write_stats(double* stage_ms, int capacity);
 
-/* ---- vertex colours (csrc/slmeshcolor.inl, which states the definition) ----
+/* ---- vertex colours (csrc/slmeshcolor.inl, which states the definition; the
+ * coloured PLY is written by csrc/slmeshwrite.inl, with the other writers) ----
  * Open3D's Poisson returns vertex_colors when the cloud has colours and its PLY
  * writer stores them as uchar red green blue; restated order-free (parity with
  * Open3D is unpinned; exact against tests/meshcolor_oracle.py).  Blocking on

@@ -1,5 +1,5 @@
 """Vertex colours (mesh.transfer_colors and the coloured .ply of
-mesh.write_triangle_mesh; csrc/slmeshcolor.inl) on the Poisson mesh of a
+mesh.write_triangle_mesh; csrc/slmeshcolor.inl, csrc/slmeshwrite.inl) on the Poisson mesh of a
 synthetic closed surface: a unit sphere of ``--points`` coloured points with
 outward normals, meshed at ``--depths``.
 

@@ -2274,11 +2274,11 @@ int sl_merge_pool_poison(int byte, int64_t* poisoned_bytes) {
 }  // extern "C"
 
 // The feature files, one translation unit with the above.  Each uses this file and slprim.inl (the primitives more
-// than one of them uses) and no other feature file, with one exception: slplane.inl uses slreg.inl's draw.
+// than one of them uses) and no other feature file.
 #include "slprim.inl"
 // global registration (FPFH, feature matching, RANSAC)
 #include "slreg.inl"
-// plane RANSAC of the per-view background removal (uses slreg.inl's draw)
+// plane RANSAC of the per-view background removal
 #include "slplane.inl"
 // Poisson meshing
 #include "slmesh.inl"
@@ -2293,9 +2293,10 @@ int sl_merge_pool_poison(int byte, int64_t* poisoned_bytes) {
 #include "slbpa.inl"
 // mesh clean-up: connected components of triangles, mask removal, vertex clustering
 #include "slmeshclean.inl"
-// mesh output: triangle and vertex normals, STL and PLY records packed on the device and streamed to the file
+// mesh output: triangle and vertex normals, STL, PLY and coloured-PLY records (slrecord.h) packed on the device and
+// streamed to the file
 #include "slmeshwrite.inl"
-// vertex colours: cloud-to-mesh transfer by tiers of nearest samples, the coloured PLY vertex record
+// vertex colours: cloud-to-mesh transfer by tiers of nearest samples
 #include "slmeshcolor.inl"
 // mesh smoothing: the vertex adjacency list (CSR), the simple, Laplacian and Taubin filters
 #include "slmeshsmooth.inl"

@@ -1,6 +1,7 @@
 // libslgpu.so, part 2k -- vertex colours for a mesh, included at the end of
-// slmerge.hip after slmeshwrite.inl (one translation unit: it uses that file's
-// scratch pool, search grid, sort and compaction, and slmeshwrite.inl's ring).
+// slmerge.hip (one translation unit: it uses that file's scratch pool, search
+// grid, sort and compaction).  The colour transfer alone: the coloured PLY that
+// takes its result is written by slmeshwrite.inl.
 // Open3D's create_from_point_cloud_poisson returns vertex_colors when the cloud
 // has colours, ball pivoting keeps the input points' colours, and
 // o3d.io.write_triangle_mesh writes them as uchar red green blue.  Open3D is not
@@ -50,15 +51,6 @@
 // same bits.  Not done: staging the candidate cells through LDS for the lower
 // tiers (one wave per run of queries in a cell, slcluster.inl's shape);
 // DESIGN.md 5.13 says what was measured without it.
-//
-// Coloured PLY.  The vertex record has 51 bytes: six doubles, then red green blue
-// as uchar from the BGR storage.  A workgroup builds the image of 256 records in
-// LDS (13 056 B = 816 lines of 16) and stores it lane-linear like the face
-// packer.  Record r starts at byte 51 r, i.e. at byte (3 r) mod 4 of a dword; wave
-// k takes the records r = 4 lane + k, so the shape of a record's writes -- bytes
-// up to the dword boundary, twelve dwords, trailing bytes -- is wave-uniform and
-// the lanes' stride is 51 dwords: odd, so ds_write_b32 meets no bank conflict.
-// The ring's slots hold chunk 51 bytes for this writer (chunk vertices a slot).
 
 namespace {
 namespace mcol {
@@ -66,7 +58,6 @@ namespace mcol {
 constexpr int kColK = 16;       // largest k
 constexpr int kStatTiers = 16;  // tiers the stats list one by one
 constexpr int kStats = 5 + kStatTiers;
-constexpr int kColRec = 51, kColLines = kT * kColRec / 16;  // 816
 
 thread_local double tls_stats[kStats];  // tiers run, filled, grid ms, query ms, resolved per tier, wave tiers
 
@@ -277,75 +268,6 @@ __global__ __launch_bounds__(kT) void k_vc_query_wave(const double* __restrict__
   if (tier) tier[qi] = static_cast<uint8_t>(tier_no);
 }
 
-// Bytes i .. i + 3 of a record held as dwords (w has one dword of zero padding past the record).
-template <int I, int N>
-__device__ __forceinline__ uint32_t rec_bytes(const uint32_t (&w)[N]) {
-  constexpr int d = I / 4, sh = 8 * (I % 4);
-  if constexpr (sh == 0) return w[d];
-  else return (w[d] >> sh) | (w[d + 1] << (32 - sh));
-}
-
-template <int HEAD, int W, int N>
-__device__ __forceinline__ void put_words(unsigned char* o, const uint32_t (&w)[N]) {
-  if constexpr (W < (kColRec - HEAD) / 4) {
-    *reinterpret_cast<uint32_t*>(o + HEAD + 4 * W) = rec_bytes<HEAD + 4 * W>(w);
-    put_words<HEAD, W + 1>(o, w);
-  }
-}
-
-// One 51-byte record at a start with HEAD bytes to the next dword boundary: those bytes, dwords, the rest.
-template <int HEAD, int N>
-__device__ __forceinline__ void put_vertex(unsigned char* o, const uint32_t (&w)[N]) {
-  if constexpr (HEAD & 1) o[0] = static_cast<unsigned char>(rec_bytes<0>(w));
-  if constexpr ((HEAD & 2) != 0) *reinterpret_cast<uint16_t*>(o + (HEAD & 1)) = static_cast<uint16_t>(rec_bytes<(HEAD & 1)>(w));
-  put_words<HEAD, 0>(o, w);
-  constexpr int words = (kColRec - HEAD) / 4, tail = (kColRec - HEAD) % 4, at = HEAD + 4 * words;  // 12 / 3, 2, 1, 0
-  if constexpr ((tail & 2) != 0) *reinterpret_cast<uint16_t*>(o + at) = static_cast<uint16_t>(rec_bytes<at>(w));
-  if constexpr ((tail & 1) != 0) o[at + (tail & 2)] = static_cast<unsigned char>(rec_bytes<at + (tail & 2)>(w));
-}
-
-// Coloured PLY vertex records of the vertices v0 .. v0 + count - 1 -> out (16-byte aligned, room for whole
-// workgroups): x y z nx ny nz, red green blue.
-__global__ __launch_bounds__(kT) void k_vc_pack_vertices(const double* __restrict__ verts,
-                                                         const int64_t* __restrict__ sums,
-                                                         const uint8_t* __restrict__ bgr, int64_t v0, int64_t count,
-                                                         uint4* __restrict__ out) {
-  __shared__ uint4 img4[kColLines];
-  unsigned char* img = reinterpret_cast<unsigned char*>(img4);
-  const int t = threadIdx.x;
-  const int k = t >> 6, r = 4 * (t & 63) + k;
-  const int64_t first = static_cast<int64_t>(blockIdx.x) * kT;
-  uint32_t w[14];
-#pragma unroll
-  for (int i = 0; i < 14; ++i) w[i] = 0u;
-  if (first + r < count) {
-    const int64_t v = v0 + first + r;
-    double n[3];
-    mwr::vn_of(sums, v, n);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      const uint64_t p = static_cast<uint64_t>(__double_as_longlong(verts[3 * v + i]));
-      const uint64_t u = static_cast<uint64_t>(__double_as_longlong(n[i]));
-      w[2 * i] = static_cast<uint32_t>(p);
-      w[2 * i + 1] = static_cast<uint32_t>(p >> 32);
-      w[6 + 2 * i] = static_cast<uint32_t>(u);
-      w[7 + 2 * i] = static_cast<uint32_t>(u >> 32);
-    }
-    w[12] = static_cast<uint32_t>(bgr[3 * v + 2]) | (static_cast<uint32_t>(bgr[3 * v + 1]) << 8) |
-            (static_cast<uint32_t>(bgr[3 * v]) << 16);
-  }
-  unsigned char* o = img + kColRec * r;
-  switch (k) {  // (wave-uniform) record start mod 4: 0, 3, 2, 1
-    case 0: put_vertex<0>(o, w); break;
-    case 1: put_vertex<1>(o, w); break;
-    case 2: put_vertex<2>(o, w); break;
-    default: put_vertex<3>(o, w); break;
-  }
-  __syncthreads();
-  const int live = static_cast<int>(min<int64_t>(kT, count - first));
-  mwr::store_lines(img4, live * kColRec, out + static_cast<int64_t>(blockIdx.x) * kColLines);
-}
-
 // A tier goes to the wave kernel when the 27 cells around a query hold kWavePoints points on average: the results
 // are the same, so the choice is about time alone.
 constexpr int64_t kWavePoints = 512;
@@ -470,24 +392,6 @@ int sl_mesh_transfer_colors_stats(double* stats, int capacity) {
   if (capacity < 0 || (capacity && !stats)) return SL_EINVAL;
   for (int i = 0; i < capacity; ++i) stats[i] = i < kStats ? tls_stats[i] : 0.0;
   return SL_OK;
-}
-
-int sl_write_mesh_ply_colors_device(sl_ctx* c, const char* path, const double* vertices, int64_t n_vertices,
-                                    const int32_t* triangles, int64_t n_triangles, const uint8_t* bgr,
-                                    int64_t chunk_triangles, void* stream) {
-  using namespace mcol;
-  if (!c) return SL_EINVAL;
-  if (n_vertices > 0 && !bgr)
-    return slgpu_fail(c, SL_EINVAL, "sl_write_mesh_ply_colors_device: bad sizes or NULL arguments");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return mwr::write_ply(
-      c, "sl_write_mesh_ply_colors_device", path, vertices, n_vertices, triangles, n_triangles, chunk_triangles, kColRec,
-      "property uchar red\nproperty uchar green\nproperty uchar blue\n",
-      [&](const int64_t* sums, int64_t v0, int64_t count, char* dev) {
-        hipLaunchKernelGGL(k_vc_pack_vertices, dim3(blocks(count)), dim3(kT), 0, s, vertices, sums, bgr, v0, count,
-                           reinterpret_cast<uint4*>(dev));
-      },
-      s);
 }
 
 }  // extern "C"

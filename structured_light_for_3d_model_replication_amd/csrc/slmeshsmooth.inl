@@ -1,7 +1,8 @@
 // libslgpu.so, part 2l -- mesh smoothing, included at the end of slmerge.hip
-// after slmeshcolor.inl (one translation unit: it shares that file's scratch
-// pool, radix sort, key runs and their starts, and slprim.inl's input checks and
-// stage clock).  Open3D users take the terraces of a scanned mesh out
+// after the mesh writers (slmeshwrite.inl) and the colour transfer
+// (slmeshcolor.inl), of which it names nothing (one translation unit: it shares
+// slmerge.hip's scratch pool, radix sort, key runs and their starts, and
+// slprim.inl's input checks and stage clock).  Open3D users take the terraces of a scanned mesh out
 // with TriangleMesh::FilterSmoothTaubin; that call, FilterSmoothSimple,
 // FilterSmoothLaplacian and the ComputeAdjacencyList they rest on are restated
 // here, for the vertices alone (normals and colours are not filtered).  Open3D

@@ -33,13 +33,16 @@
 //              element face T / property list uchar uint vertex_indices /
 //              end_header", V records of six doubles (48 bytes), T records of the
 //              byte 3 and three uint32 (13 bytes).
+//   coloured PLY      with vertex colours (BGR u8 [V][3]; slmeshcolor.inl makes
+//              them) "property uchar red / green / blue" follow nz and a vertex
+//              record has 51 bytes: the six doubles, then red green blue.
 //
-// Packing.  Neither 50 nor 13 is a multiple of 4: a thread per record storing to
-// global memory would scatter 1- and 2-byte stores.  A workgroup of 256 threads
-// builds the image of 256 records in LDS (12 800 B / 3 328 B, multiples of 16)
-// and, after one barrier, stores it lane-linear in 16-byte lines (1 KiB per wave
-// store) to the 16-byte-aligned slot.  The LDS writes are free of bank conflicts
-// (ds_write_b32: bank = dword mod 32 within a 32-lane half):
+// Packing.  None of 50, 13 and 51 is a multiple of 4: a thread per record storing
+// to global memory would scatter 1- and 2-byte stores.  A workgroup of 256 threads
+// builds the image of 256 records in LDS (12 800 B / 3 328 B / 13 056 B,
+// multiples of 16) and, after one barrier, stores it lane-linear in 16-byte lines
+// (1 KiB per wave store) to the 16-byte-aligned slot.  The LDS writes are free of
+// bank conflicts (ds_write_b32: bank = dword mod 32 within a 32-lane half):
 //   STL   two records are 25 dwords.  The even record of pair p is dwords 25 p ..
 //         25 p + 11 and the low half of dword 25 p + 12, which is its zero
 //         attribute; the odd one starts in the high half of that dword and ends
@@ -49,12 +52,15 @@
 //         take the even records and 128..255 the odd ones, so a wave writes one
 //         dword per lane at a stride of 25 dwords: 32 consecutive p give 32
 //         different banks.
-//   PLY   four faces are 13 dwords; record r starts at byte r mod 4 of a dword.
-//         Wave k takes the records with r mod 4 == k (r = 4 lane + k), so the
-//         shape of a record's writes -- leading bytes up to the dword boundary,
-//         whole dwords, trailing bytes -- is wave-uniform and the stride is 13
-//         dwords: conflict-free again.  The partial dwords are written as 1- and
-//         2-byte LDS stores by the two records that share them.
+//   PLY   faces and coloured vertices, one packer (pack_quarters over slrecord.h's
+//         put_record_at).  Four records of REC bytes are REC dwords; record r
+//         starts at byte (REC r) mod 4 of a dword: r mod 4 for a face, (3 r) mod 4
+//         for a vertex.  Wave k takes the records with r mod 4 == k (r = 4 lane +
+//         k), so the shape of a record's writes -- leading bytes up to the dword
+//         boundary, whole dwords, trailing bytes -- is wave-uniform and the lanes'
+//         stride is REC dwords, 13 or 51: odd, so conflict-free again.  The
+//         partial dwords are written as 1- and 2-byte LDS stores by the two
+//         records that share them.
 // The threads of a wave read every second (fourth) index triple; the waves of
 // the workgroup touch the same lines, which the vector cache serves.
 //
@@ -65,13 +71,16 @@
 
 #include <string>
 
+#include "slrecord.h"
+
 namespace {
 namespace mwr {
 
 constexpr int64_t kChunkTriangles = 655360;                      // 32 768 000 B of STL records
 constexpr int64_t kMaxChunkTriangles = 8 * kChunkTriangles;
-constexpr int kStlRec = 50, kFaceRec = 13, kVertexRec = 48;
-constexpr int kStlLines = kT * kStlRec / 16, kFaceLines = kT * kFaceRec / 16;  // 800, 208
+constexpr int kStlRec = 50, kFaceRec = 13, kVertexRec = 48, kColRec = 51;
+// 16-byte lines of a workgroup's image: 800, 208, 816
+constexpr int kStlLines = kT * kStlRec / 16, kFaceLines = kT * kFaceRec / 16, kColLines = kT * kColRec / 16;
 constexpr double kVnFix = 1099511627776.0;                       // 2^40
 constexpr double kVnFixMax = 4611686018427387904.0;              // 2^62
 
@@ -198,53 +207,35 @@ __global__ __launch_bounds__(kT) void k_mw_pack_stl(const double* __restrict__ v
   store_lines(img4, live * kStlRec, out + static_cast<int64_t>(blockIdx.x) * kStlLines);
 }
 
-// Bytes i .. i + 3 of the 13-byte face record (lo: bytes 0-7, hi: bytes 8-12), zero beyond it.
-__device__ __forceinline__ uint32_t face_bytes(uint64_t lo, uint64_t hi, int i) {
-  if (i == 0) return static_cast<uint32_t>(lo);
-  if (i < 8) return static_cast<uint32_t>((lo >> (8 * i)) | (hi << (64 - 8 * i)));
-  return static_cast<uint32_t>(hi >> (8 * (i - 8)));
+// The quarter-interleaved packers' common part (the header's PLY paragraph): thread t has record r = 4 (t mod 64) +
+// t / 64 of the workgroup's 256 records of REC bytes.  fill(i, w) puts record i < count of the chunk into w as
+// dwords in memory order; a record past count stays zero.  After the barrier the live records' lines go to `out`.
+template <int REC, class Fill>
+__device__ __forceinline__ void pack_quarters(uint4 (&img4)[kT * REC / 16], int64_t count, uint4* __restrict__ out,
+                                              Fill fill) {
+  const int t = threadIdx.x, r = 4 * (t & 63) + (t >> 6);
+  const int64_t first = static_cast<int64_t>(blockIdx.x) * kT;
+  uint32_t w[(REC + 3) / 4 + 1] = {};
+  if (first + r < count) fill(first + r, w);
+  slrecord::put_record_at<REC>(reinterpret_cast<unsigned char*>(img4), r, w);  // (wave-uniform shapes)
+  __syncthreads();
+  const int live = static_cast<int>(min<int64_t>(kT, count - first));
+  store_lines(img4, live * REC, out + static_cast<int64_t>(blockIdx.x) * (kT * REC / 16));
 }
 
-// One record's 13 bytes at img + 13 r with r mod 4 == K: bytes up to the dword boundary, dwords, the rest.
-template <int K>
-__device__ __forceinline__ void put_face(unsigned char* o, uint64_t lo, uint64_t hi) {
-  constexpr int head = (4 - K) & 3;  // 0, 3, 2, 1
-  if (head & 1) o[0] = static_cast<unsigned char>(face_bytes(lo, hi, 0));
-  if (head & 2) *reinterpret_cast<uint16_t*>(o + (head & 1)) = static_cast<uint16_t>(face_bytes(lo, hi, head & 1));
-  constexpr int words = (kFaceRec - head) / 4, tail = (kFaceRec - head) % 4;  // 3/1, 2/2, 2/3, 3/0
-#pragma unroll
-  for (int w = 0; w < words; ++w) *reinterpret_cast<uint32_t*>(o + head + 4 * w) = face_bytes(lo, hi, head + 4 * w);
-  constexpr int at = head + 4 * words;
-  if (tail & 2) *reinterpret_cast<uint16_t*>(o + at) = static_cast<uint16_t>(face_bytes(lo, hi, at));
-  if (tail & 1) o[at + (tail & 2)] = static_cast<unsigned char>(face_bytes(lo, hi, at + (tail & 2)));
-}
-
-// PLY face records of the triangles t0 .. t0 + count - 1 -> out (as k_mw_pack_stl).
+// PLY face records of the triangles t0 .. t0 + count - 1 -> out (as k_mw_pack_stl): the byte 3, then a b c.
 __global__ __launch_bounds__(kT) void k_mw_pack_faces(const int32_t* __restrict__ tris, int64_t t0, int64_t count,
                                                       uint4* __restrict__ out) {
   __shared__ uint4 img4[kFaceLines];
-  unsigned char* img = reinterpret_cast<unsigned char*>(img4);
-  const int t = threadIdx.x;
-  const int k = t >> 6, r = 4 * (t & 63) + k;
-  const int64_t first = static_cast<int64_t>(blockIdx.x) * kT;
-  uint64_t lo = 0, hi = 0;
-  if (first + r < count) {
-    const int64_t g = t0 + first + r;
-    const uint64_t a = static_cast<uint32_t>(tris[3 * g]), b = static_cast<uint32_t>(tris[3 * g + 1]),
+  pack_quarters<kFaceRec>(img4, count, out, [&](int64_t i, uint32_t (&w)[5]) {
+    const int64_t g = t0 + i;
+    const uint32_t a = static_cast<uint32_t>(tris[3 * g]), b = static_cast<uint32_t>(tris[3 * g + 1]),
                    c = static_cast<uint32_t>(tris[3 * g + 2]);
-    lo = 3u | (a << 8) | (b << 40);
-    hi = (b >> 24) | (c << 8);
-  }
-  unsigned char* o = img + kFaceRec * r;
-  switch (k) {  // (wave-uniform)
-    case 0: put_face<0>(o, lo, hi); break;
-    case 1: put_face<1>(o, lo, hi); break;
-    case 2: put_face<2>(o, lo, hi); break;
-    default: put_face<3>(o, lo, hi); break;
-  }
-  __syncthreads();
-  const int live = static_cast<int>(min<int64_t>(kT, count - first));
-  store_lines(img4, live * kFaceRec, out + static_cast<int64_t>(blockIdx.x) * kFaceLines);
+    w[0] = 3u | (a << 8);
+    w[1] = (a >> 24) | (b << 8);
+    w[2] = (b >> 24) | (c << 8);
+    w[3] = c >> 24;
+  });
 }
 
 // PLY vertex records of the vertices v0 .. v0 + count - 1: x y z nx ny nz, one double per thread.
@@ -262,6 +253,31 @@ __global__ __launch_bounds__(kT) void k_mw_pack_vertices(const double* __restric
     vn_of(sums, v, n);
     out[i] = n[k - 3];
   }
+}
+
+// Coloured PLY vertex records of the vertices v0 .. v0 + count - 1 -> out (as k_mw_pack_stl): x y z nx ny nz, then
+// red green blue from the BGR storage.
+__global__ __launch_bounds__(kT) void k_vc_pack_vertices(const double* __restrict__ verts,
+                                                         const int64_t* __restrict__ sums,
+                                                         const uint8_t* __restrict__ bgr, int64_t v0, int64_t count,
+                                                         uint4* __restrict__ out) {
+  __shared__ uint4 img4[kColLines];
+  pack_quarters<kColRec>(img4, count, out, [&](int64_t i, uint32_t (&w)[14]) {
+    const int64_t v = v0 + i;
+    double n[3];
+    vn_of(sums, v, n);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const uint64_t p = static_cast<uint64_t>(__double_as_longlong(verts[3 * v + k]));
+      const uint64_t u = static_cast<uint64_t>(__double_as_longlong(n[k]));
+      w[2 * k] = static_cast<uint32_t>(p);
+      w[2 * k + 1] = static_cast<uint32_t>(p >> 32);
+      w[6 + 2 * k] = static_cast<uint32_t>(u);
+      w[7 + 2 * k] = static_cast<uint32_t>(u >> 32);
+    }
+    w[12] = static_cast<uint32_t>(bgr[3 * v + 2]) | (static_cast<uint32_t>(bgr[3 * v + 1]) << 8) |
+            (static_cast<uint32_t>(bgr[3 * v]) << 16);
+  });
 }
 
 // ---- host
@@ -287,13 +303,12 @@ int vertex_sums(sl_ctx* c, const double* vertices, int64_t n_v, const int32_t* t
   return SL_OK;
 }
 
-// The PLY writer of `what`: the index check, the vertex sums, the header (vertex_props: property lines after nz),
-// then vertex chunks of `vrec`-byte records packed by pack_v(sums, v0, count, dev) and the face chunks.  A slot
-// holds chunk faces, and chunk 50 / 48 vertices of 48 bytes (the STL writer's slots) or chunk vertices of more.
-template <class PackV>
+// The PLY writer of `what`: the index check, the vertex sums, the header, then the vertex chunks and the face chunks.
+// bgr NULL: the plain 48-byte vertex records; else the 51-byte ones with their three property lines after nz.  A
+// slot holds chunk faces, and chunk 50 / 48 plain vertices (the STL writer's slots) or chunk coloured ones.
 int write_ply(sl_ctx* c, const char* what, const char* path, const double* vertices, int64_t n_vertices,
-              const int32_t* triangles, int64_t n_triangles, int64_t chunk_triangles, int vrec,
-              const char* vertex_props, PackV pack_v, hipStream_t s) {
+              const int32_t* triangles, int64_t n_triangles, const uint8_t* bgr, int64_t chunk_triangles,
+              hipStream_t s) {
   const std::string name(what);
   const int64_t chunk = chunk_of(chunk_triangles);
   if (bad_mesh(vertices, n_vertices, triangles, n_triangles) || chunk < 0)
@@ -304,7 +319,8 @@ int write_ply(sl_ctx* c, const char* what, const char* path, const double* verti
   int r = prim::require_indices(c, triangles, n_triangles, n_vertices, (name + ": triangle index out of range").c_str(),
                                s);
   if (r) return r;
-  const int64_t vchunk = vrec == kVertexRec ? chunk * kStlRec / kVertexRec : chunk;
+  const int vrec = bgr ? kColRec : kVertexRec;
+  const int64_t vchunk = bgr ? chunk : chunk * kStlRec / kVertexRec;
   slstream::Ring* ring = slgpu_file_ring(c);
   MTRY(c, slstream::ring_reserve(ring, std::max(chunk * kStlRec, vchunk * vrec)));
   DBuf<int64_t> sums;
@@ -317,18 +333,24 @@ int write_ply(sl_ctx* c, const char* what, const char* path, const double* verti
                           "property double x\nproperty double y\nproperty double z\n"
                           "property double nx\nproperty double ny\nproperty double nz\n%s"
                           "element face %lld\nproperty list uchar uint vertex_indices\nend_header\n",
-                          static_cast<long long>(n_vertices), vertex_props, static_cast<long long>(n_triangles));
+                          static_cast<long long>(n_vertices),
+                          bgr ? "property uchar red\nproperty uchar green\nproperty uchar blue\n" : "",
+                          static_cast<long long>(n_triangles));
   const int64_t nvc = (n_vertices + vchunk - 1) / vchunk, nfc = (n_triangles + chunk - 1) / chunk;
   auto v_in = [&](int64_t k) { return std::min(vchunk, n_vertices - k * vchunk); };
   auto f_in = [&](int64_t k) { return std::min(chunk, n_triangles - k * chunk); };
   return slstream::write_chunks(
       c, what, path, head, static_cast<size_t>(hl), ring, nvc + nfc,
       [&](int64_t k, char* dev) {
-        if (k < nvc)
-          pack_v(sums.p, k * vchunk, v_in(k), dev);
-        else
+        if (k >= nvc)
           hipLaunchKernelGGL(k_mw_pack_faces, dim3(blocks(f_in(k - nvc))), dim3(kT), 0, s, triangles,
                              (k - nvc) * chunk, f_in(k - nvc), reinterpret_cast<uint4*>(dev));
+        else if (bgr)
+          hipLaunchKernelGGL(k_vc_pack_vertices, dim3(blocks(v_in(k))), dim3(kT), 0, s, vertices, sums.p, bgr,
+                             k * vchunk, v_in(k), reinterpret_cast<uint4*>(dev));
+        else
+          hipLaunchKernelGGL(k_mw_pack_vertices, dim3(blocks(6 * v_in(k))), dim3(kT), 0, s, vertices, sums.p,
+                             k * vchunk, v_in(k), reinterpret_cast<double*>(dev));
       },
       [&](int64_t k) { return k < nvc ? v_in(k) * vrec : f_in(k - nvc) * kFaceRec; }, s, tls_ms);
 }
@@ -413,16 +435,20 @@ int sl_write_stl_device(sl_ctx* c, const char* path, const double* vertices, int
 
 int sl_write_mesh_ply_device(sl_ctx* c, const char* path, const double* vertices, int64_t n_vertices,
                              const int32_t* triangles, int64_t n_triangles, int64_t chunk_triangles, void* stream) {
-  using namespace mwr;
   if (!c) return SL_EINVAL;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return write_ply(
-      c, "sl_write_mesh_ply_device", path, vertices, n_vertices, triangles, n_triangles, chunk_triangles, kVertexRec, "",
-      [&](const int64_t* sums, int64_t v0, int64_t count, char* dev) {
-        hipLaunchKernelGGL(k_mw_pack_vertices, dim3(blocks(6 * count)), dim3(kT), 0, s, vertices, sums, v0, count,
-                           reinterpret_cast<double*>(dev));
-      },
-      s);
+  return mwr::write_ply(c, "sl_write_mesh_ply_device", path, vertices, n_vertices, triangles, n_triangles, nullptr,
+                        chunk_triangles, static_cast<hipStream_t>(stream));
+}
+
+int sl_write_mesh_ply_colors_device(sl_ctx* c, const char* path, const double* vertices, int64_t n_vertices,
+                                    const int32_t* triangles, int64_t n_triangles, const uint8_t* bgr,
+                                    int64_t chunk_triangles, void* stream) {
+  if (!c) return SL_EINVAL;
+  if (n_vertices > 0 && !bgr)
+    return slgpu_fail(c, SL_EINVAL, "sl_write_mesh_ply_colors_device: bad sizes or NULL arguments");
+  static const uint8_t no_vertices[3] = {};  // V <= 0 and no colours: nothing reads them, the file is a coloured one
+  return mwr::write_ply(c, "sl_write_mesh_ply_colors_device", path, vertices, n_vertices, triangles, n_triangles,
+                        bgr ? bgr : no_vertices, chunk_triangles, static_cast<hipStream_t>(stream));
 }
 
 int sl_mesh_write_stats(double* stage_ms, int capacity) {

@@ -2,14 +2,14 @@
 // (server/processing.py:25-52, page 2 of the reference GUI): Open3D's
 // PointCloud::SegmentPlane, included at the end of slmerge.hip (one translation
 // unit: it shares that file's scan / compact kernels and scratch pool,
-// slreg.inl's draw, and slprim.inl's chunk shape, tree and fold kernel of the
+// and slprim.inl's draw and the chunk shape, tree and fold kernel of the
 // ordered sum defined below).  Open3D is not in this image: the algorithm is restated
 // from its published source (geometry/PointCloudSegmentation.cpp), parity with
 // Open3D is UNPINNED, and tests/plane_oracle.py is the CPU restatement the
 // tests check against bit for bit.  All arithmetic is f64, uncontracted, in
 // the order written here.
 //
-//   draw: iteration i samples point reg::draw(seed, ransac_n * i + k, n),
+//   draw: iteration i samples point prim::draw(seed, ransac_n * i + k, n),
 //     k = 0 .. ransac_n - 1.  Duplicates are not redrawn (deviation 1: Open3D
 //     samples without replacement).
 //   hypothesis, ransac_n == 3: e0 = p1 - p0, e1 = p2 - p0, n = e0 x e1 =
@@ -101,9 +101,9 @@ __global__ __launch_bounds__(kT) void k_plane_hyp(const double* __restrict__ xyz
   double pl[4];
   bool ok;
   if (rn == 3) {
-    const reg::D3 p0 = reg::ld3(xyz, reg::draw(seed, base, un));
-    const reg::D3 p1 = reg::ld3(xyz, reg::draw(seed, base + 1, un));
-    const reg::D3 p2 = reg::ld3(xyz, reg::draw(seed, base + 2, un));
+    const prim::D3 p0 = prim::ld3(xyz, prim::draw(seed, base, un));
+    const prim::D3 p1 = prim::ld3(xyz, prim::draw(seed, base + 1, un));
+    const prim::D3 p2 = prim::ld3(xyz, prim::draw(seed, base + 2, un));
     const double e0x = p1.x - p0.x, e0y = p1.y - p0.y, e0z = p1.z - p0.z;
     const double e1x = p2.x - p0.x, e1y = p2.y - p0.y, e1z = p2.z - p0.z;
     double nx = e0y * e1z - e0z * e1y, ny = e0z * e1x - e0x * e1z, nz = e0x * e1y - e0y * e1x;
@@ -123,7 +123,7 @@ __global__ __launch_bounds__(kT) void k_plane_hyp(const double* __restrict__ xyz
   } else {
     double c[3] = {0.0, 0.0, 0.0}, m[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     for (int k = 0; k < rn; ++k) {
-      const reg::D3 p = reg::ld3(xyz, reg::draw(seed, base + k, un));
+      const prim::D3 p = prim::ld3(xyz, prim::draw(seed, base + k, un));
       c[0] += p.x;
       c[1] += p.y;
       c[2] += p.z;
@@ -133,7 +133,7 @@ __global__ __launch_bounds__(kT) void k_plane_hyp(const double* __restrict__ xyz
     c[1] /= dm;
     c[2] /= dm;
     for (int k = 0; k < rn; ++k) {
-      const reg::D3 p = reg::ld3(xyz, reg::draw(seed, base + k, un));
+      const prim::D3 p = prim::ld3(xyz, prim::draw(seed, base + k, un));
       const double rx = p.x - c[0], ry = p.y - c[1], rz = p.z - c[2];
       m[0] += rx * rx;
       m[1] += rx * ry;

@@ -168,6 +168,21 @@ int require_indices(sl_ctx* c, const int32_t* tris, int64_t n_t, int64_t n_v, co
   });
 }
 
+// -------------------------------------------------------------------- draw ----
+struct D3 {
+  double x, y, z;
+};
+__device__ __forceinline__ D3 ld3(const double* p, int64_t i) { return {p[3 * i], p[3 * i + 1], p[3 * i + 2]}; }
+
+// the n-th random index below nc of the RANSACs (splitmix64 of seed + (n + 1) golden)
+__device__ __forceinline__ int64_t draw(uint64_t seed, uint64_t n, uint64_t nc) {
+  uint64_t z = seed + (n + 1) * 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  z ^= z >> 31;
+  return static_cast<int64_t>(((z >> 32) * nc) >> 32);
+}
+
 // ------------------------------------------------------------- ordered sum ----
 constexpr int kRows = 16;           // rows of a chunk each lane holds
 constexpr int kChunk = kT * kRows;  // 4096 points

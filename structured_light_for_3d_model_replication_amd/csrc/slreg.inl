@@ -105,9 +105,7 @@ __device__ double atan2_det(double y, double x) {
   }
 }
 
-struct D3 {
-  double x, y, z;
-};
+using prim::D3, prim::ld3, prim::draw;  // the point triple and the sampler slplane.inl draws with as well
 __device__ __forceinline__ double dot3(D3 a, D3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
 __device__ __forceinline__ double norm3(D3 a) { return sqrt(dot3(a, a)); }
 __device__ __forceinline__ D3 cross3(D3 a, D3 b) {
@@ -294,17 +292,6 @@ __device__ __forceinline__ D3 tp(const double* T, D3 p) {
   return {((T[0] * p.x + T[1] * p.y) + T[2] * p.z) + T[3], ((T[4] * p.x + T[5] * p.y) + T[6] * p.z) + T[7],
           ((T[8] * p.x + T[9] * p.y) + T[10] * p.z) + T[11]};
 }
-
-// the n-th random correspondence index (splitmix64 of seed + (n + 1) golden)
-__device__ __forceinline__ int64_t draw(uint64_t seed, uint64_t n, uint64_t nc) {
-  uint64_t z = seed + (n + 1) * 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  return static_cast<int64_t>(((z >> 32) * nc) >> 32);
-}
-
-__device__ __forceinline__ D3 ld3(const double* p, int64_t i) { return {p[3 * i], p[3 * i + 1], p[3 * i + 2]}; }
 
 }  // namespace reg
 

@@ -1,5 +1,5 @@
 // libslgpu.so -- how a file's body leaves device memory in chunks, included by slgpu.hip (which owns the ring in
-// sl_ctx and writes the host PLY files with put_all) and slmerge.hip (slmeshwrite.inl, slmeshcolor.inl): two
+// sl_ctx and writes the host PLY files with put_all) and slmerge.hip (slmeshwrite.inl, which holds every mesh writer): two
 // translation units of one library, hence a named namespace and inline functions.
 //
 // The body of a file never exists on the host as a whole.  A context owns one Ring of kRing slots, each a device

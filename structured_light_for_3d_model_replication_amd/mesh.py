@@ -899,7 +899,7 @@ def _write_host(path, ext, vertices, triangles, colors=None):
 
 
 def _write_device(path, ext, vertices, triangles, chunk_triangles=0, colors=None):
-    """The device writers (csrc/slmeshwrite.inl, csrc/slmeshcolor.inl).  ``path`` None: packed and copied back, no
+    """The device writers (csrc/slmeshwrite.inl, the coloured PLY included).  ``path`` None: packed and copied back, no
     file (measurement)."""
     eng, V, T = _mesh_args(vertices, triangles, vertices.device)
     name = "sl_write_mesh_ply_device" if ext == ".ply" else "sl_write_stl_device"

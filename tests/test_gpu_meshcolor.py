@@ -1,5 +1,5 @@
-"""Vertex colours on the GPU (csrc/slmeshcolor.inl) against tests/meshcolor_oracle.py: the colour transfer exactly,
-the coloured PLY byte for byte, the drop-ins end to end.  Every result is computed twice and required to repeat."""
+"""Vertex colours on the GPU (csrc/slmeshcolor.inl; the coloured PLY: csrc/slmeshwrite.inl) against
+tests/meshcolor_oracle.py: the colour transfer exactly, the coloured PLY byte for byte, the drop-ins end to end.  Every result is computed twice and required to repeat."""
 import functools
 
 import numpy as np
