@@ -742,6 +742,65 @@ int sl_mesh_smooth(sl_ctx* ctx, const double* vertices, int64_t n_vertices, cons
                    double* out_vertices, void* stream);
 int sl_mesh_smooth_stats(double* stage_ms, int capacity);
 
+/* ---- mesh checks (csrc/slmeshcheck.inl, which states the definitions) ----
+ * Open3D's is_edge_manifold / is_vertex_manifold / is_orientable / is_watertight,
+ * get_non_manifold_edges / _vertices, orient_triangles, get_surface_area,
+ * get_volume, remove_degenerate_triangles and remove_duplicated_triangles,
+ * restated order-free (parity with Open3D is unpinned; exact against
+ * tests/meshcheck_oracle.py).  triangles int32 [n_triangles][3], vertices f64
+ * [n_vertices][3] (device); n_vertices < 2^31, 3 n_triangles < 2^32.  A pass of
+ * its own reads every index first: one outside 0 .. n_vertices - 1 is SL_EINDEX
+ * and nothing is indexed.  Zero triangles succeed.  Blocking on `stream`;
+ * scratch from the merge stage's pool.
+ *   Sides: (a, b, c) has a->b, b->c, c->a; a side's key is min n_vertices + max,
+ *   its direction bit from < to.  A triangle with two equal indices is
+ *   degenerate and still gives its three sides to the edge counts.  An edge of
+ *   m sides: m = 1 boundary, m = 2 regular (consistent iff the direction bits
+ *   differ), m >= 3 non-manifold.  Corners (t, k) at one vertex are joined iff
+ *   their (non-degenerate) triangles share an edge that contains the vertex; a
+ *   vertex whose corners fall into more than one class is non-manifold.
+ *   Orientable: no m >= 3 edge and a flip bit per triangle that makes every
+ *   m = 2 edge consistent (two loops {v, v} never are).
+ *   sl_mesh_check   one sort of the sides, everything from it.  counts (host,
+ *       int64 [8]): 0 unique edges, 1 boundary edges, 2 non-manifold edges,
+ *       3 inconsistent edges, 4 non-manifold vertices, 5 degenerate triangles,
+ *       6 orientable (0 / 1), 7 rows of the edge list.  Optional device outputs
+ *       (NULL: skipped, and so is their gather): edges int32 [rows][2], (min,
+ *       max) in ascending key order -- the m >= 3 edges, and with
+ *       allow_boundary_edges == 0 the m = 1 edges too (room for n_triangles rows,
+ *       or 3 n_triangles without boundary edges allowed); vertices int32
+ *       [counts[4]], ascending (room for n_vertices); oriented int32
+ *       [n_triangles][3]: per component (connected through m = 2 edges) the
+ *       smallest triangle index keeps its winding, a flipped (a, b, c) is
+ *       (a, c, b); a copy when the mesh is not orientable.
+ *   sl_mesh_check_stats   the calling thread's last sl_mesh_check or
+ *       sl_mesh_measure: host milliseconds per stage (side keys, sort, classify
+ *       and edge list, corner classes, parity unions, flips, measures;
+ *       stage_ms[capacity], zero-filled) -- a measurement aid.
+ *   sl_mesh_measure   A_t = 0.5 sqrt((n0 n0 + n1 n1) + n2 n2), n = (v1 - v0) x
+ *       (v2 - v0); W_t = ((x0 c0 + y0 c1) + z0 c2) / 6.0, c = v1 x v2 (f64,
+ *       uncontracted); *area and *signed_volume (host) are their ordered sums
+ *       (sl_ordered_sum) in triangle order.  The signed volume means a volume only
+ *       on a watertight mesh (the caller checks) and is positive iff the
+ *       windings face outward.  A non-finite vertex: SL_EINVAL.
+ *   sl_mesh_remove_degenerate   the triangles with two equal indices go, the
+ *       rest keep their order -> out_triangles (room for n_triangles rows).
+ *   sl_mesh_remove_duplicated_triangles   every triple is rotated so that its
+ *       strictly smallest index comes first (the opposite winding is another
+ *       triple); the first occurrence of every rotated triple is kept, in input
+ *       order and as it was given -> out_triangles (room for n_triangles rows). */
+int sl_mesh_check(sl_ctx* ctx, const int32_t* triangles, int64_t n_triangles, int64_t n_vertices,
+                  int allow_boundary_edges, int64_t* counts, int32_t* edges, int32_t* vertices, int32_t* oriented,
+                  void* stream);
+int sl_mesh_check_stats(double* stage_ms, int capacity);
+int sl_mesh_measure(sl_ctx* ctx, const double* vertices, int64_t n_vertices, const int32_t* triangles,
+                    int64_t n_triangles, double* area, double* signed_volume, void* stream);
+int sl_mesh_remove_degenerate(sl_ctx* ctx, const int32_t* triangles, int64_t n_triangles, int64_t n_vertices,
+                              int32_t* out_triangles, int64_t* out_n_triangles, void* stream);
+int sl_mesh_remove_duplicated_triangles(sl_ctx* ctx, const int32_t* triangles, int64_t n_triangles,
+                                        int64_t n_vertices, int32_t* out_triangles, int64_t* out_n_triangles,
+                                        void* stream);
+
 /* ---- consistent tangent-plane normal orientation (processing.py:201, :282) ----
  * orient_normals_consistent_tangent_plane restated on the kNN graph alone
  * (csrc/slorient.inl; tests/orient_oracle.py is the CPU restatement, bit for

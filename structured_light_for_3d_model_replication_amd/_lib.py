@@ -57,6 +57,8 @@ EXPORTS = ("sl_abi_version", "sl_ctx_create", "sl_ctx_destroy", "sl_ctx_last_err
            "sl_mesh_write_stats",
            "sl_mesh_transfer_colors", "sl_mesh_transfer_colors_stats", "sl_write_mesh_ply_colors_device",
            "sl_mesh_adjacency", "sl_mesh_smooth", "sl_mesh_smooth_stats",
+           "sl_mesh_check", "sl_mesh_check_stats", "sl_mesh_measure", "sl_mesh_remove_degenerate",
+           "sl_mesh_remove_duplicated_triangles",
            "sl_information_matrix", "sl_pose_graph_optimize",
            "sl_radius_count", "sl_cluster_dbscan", "sl_cluster_dbscan_stats", "sl_nearest_neighbor_distance",
            "sl_ball_pivot_max_neighbours", "sl_ball_pivot_candidates", "sl_ball_pivot_candidates_stats",
@@ -150,6 +152,12 @@ _SIGS = {
     "sl_mesh_smooth": (_i32, [_vp, _vp, _i64, _vp, _i64, _i32, _i32, ctypes.c_double, ctypes.c_double, _i32, _vp,
                               _vp]),
     "sl_mesh_smooth_stats": (_i32, [ctypes.POINTER(ctypes.c_double), _i32]),
+    "sl_mesh_check": (_i32, [_vp, _vp, _i64, _i64, _i32, ctypes.POINTER(_i64), _vp, _vp, _vp, _vp]),
+    "sl_mesh_check_stats": (_i32, [ctypes.POINTER(ctypes.c_double), _i32]),
+    "sl_mesh_measure": (_i32, [_vp, _vp, _i64, _vp, _i64, ctypes.POINTER(ctypes.c_double),
+                               ctypes.POINTER(ctypes.c_double), _vp]),
+    "sl_mesh_remove_degenerate": (_i32, [_vp, _vp, _i64, _i64, _vp, ctypes.POINTER(_i64), _vp]),
+    "sl_mesh_remove_duplicated_triangles": (_i32, [_vp, _vp, _i64, _i64, _vp, ctypes.POINTER(_i64), _vp]),
     "sl_orient_normals_mst": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, ctypes.POINTER(_i64),
                                      ctypes.POINTER(_i64), _vp]),
     "sl_orient_normals_mst_stats": (_i32, [ctypes.POINTER(_i32), ctypes.POINTER(_i32), _i32]),

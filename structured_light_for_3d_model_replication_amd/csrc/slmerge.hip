@@ -2300,3 +2300,6 @@ int sl_merge_pool_poison(int byte, int64_t* poisoned_bytes) {
 #include "slmeshcolor.inl"
 // mesh smoothing: the vertex adjacency list (CSR), the simple, Laplacian and Taubin filters
 #include "slmeshsmooth.inl"
+// mesh checks: edge and vertex manifoldness, orientability and orient_triangles, area and volume, degenerate and
+// duplicated triangles
+#include "slmeshcheck.inl"

@@ -252,41 +252,6 @@ __global__ __launch_bounds__(kT) void k_sc_avg(const uint32_t* ustart, int64_t m
   out[3 * o + 2] = p2 / cnt;
 }
 
-// rot[t]: the mapped triple rotated so that its smallest index comes first; ok[t] = 0 when two are equal
-__global__ __launch_bounds__(kT) void k_sc_tris(const int32_t* tris, int64_t n_t, const uint32_t* vmap, uint32_t* rot,
-                                                uint32_t* ok) {
-  const int64_t t = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
-  if (t >= n_t) return;
-  const uint32_t a = vmap[tris[3 * t]], b = vmap[tris[3 * t + 1]], c = vmap[tris[3 * t + 2]];
-  uint32_t r0 = a, r1 = b, r2 = c;
-  if (b < a && b < c) {
-    r0 = b;
-    r1 = c;
-    r2 = a;
-  } else if (c < a && c < b) {
-    r0 = c;
-    r1 = a;
-    r2 = b;
-  }
-  rot[3 * t] = r0;
-  rot[3 * t + 1] = r1;
-  rot[3 * t + 2] = r2;
-  ok[t] = (a != b && b != c && c != a) ? 1u : 0u;
-}
-
-// head[j] = 1 for the first occurrence (the smallest compacted position: the sorts are stable) of every triple
-__global__ __launch_bounds__(kT) void k_sc_heads(const uint32_t* tri, const uint32_t* vals, int64_t n, uint32_t* head) {
-  const int64_t i = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
-  if (i >= n) return;
-  const int64_t j = vals[i];
-  bool first = i == 0;
-  if (!first) {
-    const int64_t q = vals[i - 1];
-    first = tri[3 * j] != tri[3 * q] || tri[3 * j + 1] != tri[3 * q + 1] || tri[3 * j + 2] != tri[3 * q + 2];
-  }
-  head[j] = first ? 1u : 0u;
-}
-
 bool bad_sizes(int64_t n_v, int64_t n_t) {
   return n_v < 0 || n_t < 0 || n_v >= (1ll << 31) || 3 * n_t >= (1ll << 32);
 }
@@ -508,7 +473,7 @@ int sl_mesh_simplify_clustering(sl_ctx* c, const double* vertices, int64_t n_ver
   MTRY(c, rot.alloc(3 * nt));
   MTRY(c, ok.alloc(nt));
   MTRY(c, pos.alloc(nt));
-  hipLaunchKernelGGL(k_sc_tris, dim3(blocks(nt)), dim3(kT), 0, s, triangles, nt, vmap.p, rot.p, ok.p);
+  hipLaunchKernelGGL(prim::k_sc_tris, dim3(blocks(nt)), dim3(kT), 0, s, triangles, nt, vmap.p, rot.p, ok.p);
   MTRY(c, hipGetLastError());
   int64_t live = 0;
   r = scan_flags(c, ok.p, nt, pos.p, &live, s);
@@ -525,7 +490,7 @@ int sl_mesh_simplify_clustering(sl_ctx* c, const double* vertices, int64_t n_ver
   MTRY(c, hpos.alloc(live));
   r = sort_triples(c, tri.p, live, static_cast<uint64_t>(m), 0xffffffffu, keys.p, vals.p, s);
   if (r) return r;
-  hipLaunchKernelGGL(k_sc_heads, dim3(blocks(live)), dim3(kT), 0, s, tri.p, vals.p, live, head.p);
+  hipLaunchKernelGGL(prim::k_sc_heads, dim3(blocks(live)), dim3(kT), 0, s, tri.p, vals.p, live, head.p);
   MTRY(c, hipGetLastError());
   // the first occurrences in input order (the indices are below 2^31: the same bits as int32)
   r = compact_rows<uint32_t, 3>(c, tri.p, live, head.p, hpos.p, reinterpret_cast<uint32_t*>(out_triangles),

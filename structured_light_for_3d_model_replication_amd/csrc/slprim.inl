@@ -217,5 +217,49 @@ __global__ __launch_bounds__(kT) void k_plane_fold_sum(const double* __restrict_
   if (threadIdx.x == 0) out[blockIdx.x] = acc;
 }
 
+// ------------------------------------------------------- rotated triples ----
+// (sl_mesh_simplify_clustering's and sl_mesh_remove_duplicated_triangles' test for "the same triangle")
+// rot[t]: the mapped triple (vmap NULL: the triple itself) rotated so that its strictly smallest index comes first
+// (a triple whose smallest index occurs twice stays as it is); ok[t] = 0 when two are equal
+__global__ __launch_bounds__(kT) void k_sc_tris(const int32_t* tris, int64_t n_t, const uint32_t* vmap, uint32_t* rot,
+                                                uint32_t* ok) {
+  const int64_t t = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
+  if (t >= n_t) return;
+  uint32_t a = static_cast<uint32_t>(tris[3 * t]), b = static_cast<uint32_t>(tris[3 * t + 1]),
+           c = static_cast<uint32_t>(tris[3 * t + 2]);
+  if (vmap) {
+    a = vmap[a];
+    b = vmap[b];
+    c = vmap[c];
+  }
+  uint32_t r0 = a, r1 = b, r2 = c;
+  if (b < a && b < c) {
+    r0 = b;
+    r1 = c;
+    r2 = a;
+  } else if (c < a && c < b) {
+    r0 = c;
+    r1 = a;
+    r2 = b;
+  }
+  rot[3 * t] = r0;
+  rot[3 * t + 1] = r1;
+  rot[3 * t + 2] = r2;
+  ok[t] = (a != b && b != c && c != a) ? 1u : 0u;
+}
+
+// head[j] = 1 for the first occurrence (the smallest position: the sorts are stable) of every triple
+__global__ __launch_bounds__(kT) void k_sc_heads(const uint32_t* tri, const uint32_t* vals, int64_t n, uint32_t* head) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
+  if (i >= n) return;
+  const int64_t j = vals[i];
+  bool first = i == 0;
+  if (!first) {
+    const int64_t q = vals[i - 1];
+    first = tri[3 * j] != tri[3 * q] || tri[3 * j + 1] != tri[3 * q + 1] || tri[3 * j + 2] != tri[3 * q + 2];
+  }
+  head[j] = first ? 1u : 0u;
+}
+
 }  // namespace prim
 }  // namespace

@@ -53,6 +53,17 @@ neighbours in ascending index (csrc/slmeshsmooth.inl states the rules; exact
 against tests/meshsmooth_oracle.py).  The drop-ins apply them when asked to
 (``smooth_iterations``, ``smooth_method``, ``smooth_fixed_boundary``).
 
+``check`` says whether a mesh is printable: boundary, non-manifold and
+inconsistent edges, non-manifold vertices, orientable, watertight, area and
+volume, all from one sort of the triangles' sides (csrc/slmeshcheck.inl states
+the definitions; exact against tests/meshcheck_oracle.py).  Open3D's
+``is_edge_manifold``, ``is_vertex_manifold``, ``is_orientable``,
+``is_watertight``, ``get_non_manifold_edges``, ``get_non_manifold_vertices``,
+``get_surface_area`` and ``get_volume`` are views of it, beside
+``orient_triangles``, ``remove_degenerate_triangles`` and
+``remove_duplicated_triangles``.  The drop-ins report and repair when asked to
+(``check_mesh``, ``repair_mesh``).
+
 Open3D's Poisson is the adaptive-octree variant and is not installed here:
 parity with Open3D is unpinned, and tests/mesh_oracle.py is the CPU restatement
 the tests check against -- bit for bit for every stage except the solve.
@@ -559,6 +570,199 @@ def smooth_stats(*, device=None) -> dict:
     v = (ctypes.c_double * 4)()
     _lib.check(eng._L.sl_mesh_smooth_stats(v, 4), None, "sl_mesh_smooth_stats")
     return {"keys_ms": v[0], "sort_ms": v[1], "csr_ms": v[2], "iterations_ms": v[3]}
+
+
+def _check_args(vertices, triangles, n_vertices, device):
+    """-> (engine, vertices f64 | None, triangles int32, V): ``vertices`` may be None when ``n_vertices`` is given."""
+    eng = _engine(device)
+    Vx = None if vertices is None else _f64(vertices, eng.device)
+    if Vx is None and n_vertices is None:
+        raise ValueError("vertices or n_vertices is needed")
+    nv = len(Vx) if n_vertices is None else int(n_vertices)
+    if Vx is not None and nv != len(Vx):
+        raise ValueError("n_vertices does not match the vertices")
+    if not 0 <= nv < 2 ** 31:
+        raise ValueError("n_vertices must be in 0 .. 2^31 - 1")
+    return eng, Vx, _tris(triangles, eng.device), nv
+
+
+def _mesh_check(eng, T, nv, *, allow_boundary_edges=True, edges=False, vertices=False, orient=False) -> dict:
+    """One sl_mesh_check -> the counts and booleans, plus the lists that were asked for."""
+    t, dev = len(T), eng.device
+    allow = bool(allow_boundary_edges)
+    counts = (ctypes.c_int64 * 8)()
+    E = torch.empty((max((1 if allow else 3) * t, 1), 2), dtype=torch.int32, device=dev) if edges else None
+    L = torch.empty(max(nv, 1), dtype=torch.int32, device=dev) if vertices else None
+    O = torch.empty((max(t, 1), 3), dtype=torch.int32, device=dev) if orient else None
+    _call(eng, "sl_mesh_check", _ptr(T) if t else None, t, nv, int(allow), counts, _ptr(E), _ptr(L), _ptr(O))
+    c = {"vertices": nv, "triangles": t, "edges": counts[0], "boundary_edges": counts[1],
+         "non_manifold_edges": counts[2], "inconsistent_edges": counts[3], "non_manifold_vertices": counts[4],
+         "degenerate_triangles": counts[5]}
+    c["edge_manifold"] = counts[2] == 0
+    c["edge_manifold_closed"] = counts[2] == 0 and counts[1] == 0
+    c["vertex_manifold"] = counts[4] == 0
+    c["orientable"] = counts[6] != 0
+    c["consistent"] = counts[3] == 0
+    c["watertight"] = c["edge_manifold_closed"] and c["vertex_manifold"] and c["consistent"]
+    if edges:
+        c["edge_list"] = E[: counts[7]].clone()      # (not views of the capacities)
+    if vertices:
+        c["vertex_list"] = L[: counts[4]].clone()
+    if orient:
+        c["oriented"] = O[:t]
+    return c
+
+
+def _measure(eng, Vx, T):
+    """sl_mesh_measure -> (area, signed volume): the ordered sums of A_t and W_t in triangle order."""
+    a, w = ctypes.c_double(), ctypes.c_double()
+    _call(eng, "sl_mesh_measure", _ptr(Vx) if len(Vx) else None, len(Vx), _ptr(T) if len(T) else None, len(T),
+          ctypes.byref(a), ctypes.byref(w))
+    return a.value, w.value
+
+
+def check(vertices, triangles, *, n_vertices=None, device=None) -> dict:
+    """Everything the mesh checks know about a mesh, from one sort of its sides
+    (csrc/slmeshcheck.inl states the definitions; exact against
+    tests/meshcheck_oracle.py) -> a dict: the counts "vertices", "triangles",
+    "edges" (distinct), "boundary_edges" (one side), "non_manifold_edges" (three
+    or more sides), "inconsistent_edges" (two sides of the same direction),
+    "non_manifold_vertices" and "degenerate_triangles"; the booleans
+    "edge_manifold" (no non-manifold edge), "edge_manifold_closed" (and no
+    boundary edge), "vertex_manifold", "orientable", "consistent" (no
+    inconsistent edge) and "watertight" (closed, vertex-manifold and consistent,
+    as given); "area", and "volume" / "signed_volume" where they are defined (a
+    watertight mesh; positive signed volume: the windings face outward), else
+    None.  ``vertices`` may be None when ``n_vertices`` is given: the measures
+    are None then.  A degenerate triangle (two equal indices) gives its sides to
+    the edge counts and takes no part in the vertex test.  An index outside
+    0 .. V - 1 raises IndexError, a non-finite vertex ValueError."""
+    eng, Vx, T, nv = _check_args(vertices, triangles, n_vertices, device)
+    c = _mesh_check(eng, T, nv)
+    c["area"] = c["volume"] = c["signed_volume"] = None
+    if Vx is not None:
+        c["area"], w = _measure(eng, Vx, T)
+        if c["watertight"]:
+            c["volume"], c["signed_volume"] = abs(w), w
+    return c
+
+
+def check_stats(*, device=None) -> dict:
+    """Host milliseconds per stage of this thread's last mesh check or measure
+    (sl_mesh_check_stats; a measurement aid)."""
+    eng = _engine(device)
+    v = (ctypes.c_double * 7)()
+    _lib.check(eng._L.sl_mesh_check_stats(v, 7), None, "sl_mesh_check_stats")
+    return {"side_keys_ms": v[0], "sort_ms": v[1], "classify_ms": v[2], "corners_ms": v[3], "parity_ms": v[4],
+            "flips_ms": v[5], "measure_ms": v[6]}
+
+
+def get_non_manifold_edges(vertices, triangles, allow_boundary_edges: bool = True, *, n_vertices=None, device=None):
+    """TriangleMesh.get_non_manifold_edges -> int32 [E, 2] on the device: the
+    edges with three or more sides, and with ``allow_boundary_edges=False`` those
+    with one side too, as rows (min, max) in ascending order of min V + max.
+    Deviation: Open3D returns the order of a hash map."""
+    eng, _, T, nv = _check_args(vertices, triangles, n_vertices, device)
+    return _mesh_check(eng, T, nv, allow_boundary_edges=allow_boundary_edges, edges=True)["edge_list"]
+
+
+def get_non_manifold_vertices(vertices, triangles, *, n_vertices=None, device=None):
+    """TriangleMesh.get_non_manifold_vertices -> int32 [M] on the device,
+    ascending: the vertices whose corners fall into more than one class (two
+    corners at a vertex are joined iff their triangles share an edge that
+    contains it).  Deviation: degenerate triangles take no part."""
+    eng, _, T, nv = _check_args(vertices, triangles, n_vertices, device)
+    return _mesh_check(eng, T, nv, vertices=True)["vertex_list"]
+
+
+def is_edge_manifold(vertices, triangles, allow_boundary_edges: bool = True, *, n_vertices=None, device=None) -> bool:
+    """TriangleMesh.is_edge_manifold: no edge with three or more sides, and with
+    ``allow_boundary_edges=False`` none with one side either."""
+    eng, _, T, nv = _check_args(vertices, triangles, n_vertices, device)
+    c = _mesh_check(eng, T, nv)
+    return c["edge_manifold"] if allow_boundary_edges else c["edge_manifold_closed"]
+
+
+def is_vertex_manifold(vertices, triangles, *, n_vertices=None, device=None) -> bool:
+    """TriangleMesh.is_vertex_manifold: ``get_non_manifold_vertices`` is empty."""
+    eng, _, T, nv = _check_args(vertices, triangles, n_vertices, device)
+    return _mesh_check(eng, T, nv)["vertex_manifold"]
+
+
+def is_orientable(vertices, triangles, *, n_vertices=None, device=None) -> bool:
+    """TriangleMesh.is_orientable: no edge has three or more sides and some
+    choice of flipped triangles makes every two-sided edge consistent."""
+    eng, _, T, nv = _check_args(vertices, triangles, n_vertices, device)
+    return _mesh_check(eng, T, nv)["orientable"]
+
+
+def is_watertight(vertices, triangles, *, check_self_intersection: bool = False, n_vertices=None,
+                  device=None) -> bool:
+    """TriangleMesh.is_watertight without its self-intersection test: edge-manifold
+    with no boundary, vertex-manifold and no inconsistent edge, as given (no
+    flips are searched).  Deviation: Open3D also rejects self-intersecting
+    meshes (an O(T^2) triangle-pair loop); ``check_self_intersection=True``
+    raises NotImplementedError."""
+    if check_self_intersection:
+        raise NotImplementedError("the self-intersection test of is_watertight is not provided")
+    eng, _, T, nv = _check_args(vertices, triangles, n_vertices, device)
+    return _mesh_check(eng, T, nv)["watertight"]
+
+
+def orient_triangles(vertices, triangles, *, n_vertices=None, device=None):
+    """TriangleMesh.orient_triangles -> (triangles int32 [T, 3] on the device,
+    orientable).  Components are connected through two-sided edges; in each the
+    smallest triangle index keeps its winding and a flipped (a, b, c) becomes
+    (a, c, b).  Deviations: Open3D seeds a component from an unordered_set; when
+    the mesh is not orientable the triangles come back unchanged (Open3D leaves
+    them half flipped).  The input is never modified."""
+    eng, _, T, nv = _check_args(vertices, triangles, n_vertices, device)
+    c = _mesh_check(eng, T, nv, orient=True)
+    return c["oriented"], c["orientable"]
+
+
+def get_surface_area(vertices, triangles, *, device=None) -> float:
+    """TriangleMesh.get_surface_area: the ordered sum (``ordered_sum``) of the
+    triangles' areas in triangle order."""
+    eng, Vx, T, _ = _check_args(vertices, triangles, None, device)
+    return _measure(eng, Vx, T)[0]
+
+
+def get_volume(vertices, triangles, *, signed: bool = False, device=None) -> float:
+    """TriangleMesh.get_volume: |the ordered sum of the tetrahedra (0, v0, v1, v2)|;
+    with ``signed`` (an extension) the sum itself, positive iff the windings
+    face outward.  A mesh that is not watertight (``is_watertight``) raises
+    ValueError, as Open3D throws."""
+    eng, Vx, T, nv = _check_args(vertices, triangles, None, device)
+    if not _mesh_check(eng, T, nv)["watertight"]:
+        raise ValueError("The mesh is not watertight, and the volume cannot be computed.")
+    w = _measure(eng, Vx, T)[1]
+    return w if signed else abs(w)
+
+
+def _remove(name, vertices, triangles, n_vertices, device):
+    eng, Vx, T, nv = _check_args(vertices, triangles, n_vertices, device)
+    out = torch.empty((max(len(T), 1), 3), dtype=torch.int32, device=eng.device)
+    nt = ctypes.c_int64()
+    _call(eng, name, _ptr(T) if len(T) else None, len(T), nv, _ptr(out), ctypes.byref(nt))
+    return Vx, out[: nt.value]
+
+
+def remove_degenerate_triangles(vertices, triangles, *, n_vertices=None, device=None):
+    """TriangleMesh.remove_degenerate_triangles -> (vertices, triangles): the
+    triangles with two equal indices go, the rest keep their order; the
+    vertices are untouched."""
+    return _remove("sl_mesh_remove_degenerate", vertices, triangles, n_vertices, device)
+
+
+def remove_duplicated_triangles(vertices, triangles, *, n_vertices=None, device=None):
+    """TriangleMesh.remove_duplicated_triangles -> (vertices, triangles): two
+    triangles are the same iff their triples are equal after a rotation that puts
+    the strictly smallest index first (the opposite winding is another
+    triangle); the first occurrence of each is kept, in input order --
+    ``simplify_vertex_clustering``'s rule.  Deviation: the kept triangle is
+    stored as it was given (Open3D stores the rotated form)."""
+    return _remove("sl_mesh_remove_duplicated_triangles", vertices, triangles, n_vertices, device)
 
 
 def quantile(values, q: float) -> float:

@@ -57,6 +57,13 @@ errors, and runs them on the GPU through ``merge`` (libslgpu.so):
   csrc/slmeshsmooth.inl) after the clean-up and before the colours and the writer, with one line of the
   method, the iterations and the vertex count; without ``smooth_iterations`` nothing changes.  Deviations:
   a vertex's neighbours are summed in ascending index (Open3D: the order of an unordered_set).
+  Two more, ``check_mesh=False`` and ``repair_mesh=False`` (csrc/slmeshcheck.inl).  ``repair_mesh`` runs after the
+  clean-up and before the smoothing: ``mesh.remove_degenerate_triangles``, ``mesh.remove_duplicated_triangles``,
+  ``mesh.orient_triangles`` when the mesh is orientable, every triangle flipped when the result is watertight with
+  a negative signed volume, ``mesh.remove_unreferenced_vertices``; one ``Repair:`` line with the counts.
+  ``check_mesh`` reports on the mesh that is written, just before the writer: one ``Mesh check:`` line of
+  ``mesh.check``'s counts -- vertices, triangles, boundary and non-manifold edges, non-manifold vertices,
+  orientable, watertight, the area, and the volume when the mesh is watertight.  With both off nothing changes.
 
 Without Open3D, "a point cloud object" is a ``Cloud(points, colors)`` of
 device tensors (f64 [N, 3], BGR u8 [N, 3] or None).  It is accepted wherever
@@ -257,10 +264,49 @@ class ProcessingLogic:
         return V
 
     @staticmethod
+    def _repair_mesh(tag, V, T, repair_mesh):
+        """The opt-in repair of the drop-ins' mesh (csrc/slmeshcheck.inl): degenerate, then duplicated triangles go;
+        an orientable mesh is wound consistently (mesh.orient_triangles); a watertight one of negative signed volume
+        is turned outward; the unreferenced vertices go.  One line with the counts."""
+        if not repair_mesh:
+            return V, T
+        n0 = len(T)
+        _, T = mesh.remove_degenerate_triangles(V, T, device=V.device)
+        n1 = len(T)
+        _, T = mesh.remove_duplicated_triangles(V, T, device=V.device)
+        n2 = len(T)
+        To, orientable = mesh.orient_triangles(V, T, device=V.device)
+        flipped = int((To != T).any(1).sum()) if orientable else 0
+        T = To
+        c = mesh.check(V, T, device=V.device)
+        outward = bool(c["watertight"] and c["signed_volume"] < 0.0)
+        if outward:
+            T = T[:, [0, 2, 1]].contiguous()
+        nv = len(V)
+        V, T = mesh.remove_unreferenced_vertices(V, T, device=V.device)
+        print(f"[{tag}] Repair: {n0 - n1} degenerate and {n1 - n2} duplicated triangles removed, {flipped} flipped "
+              f"(orientable: {'yes' if orientable else 'no'}), turned outward: {'yes' if outward else 'no'}, "
+              f"{nv - len(V)} unreferenced vertices removed")
+        return V, T
+
+    @staticmethod
+    def _check_mesh(tag, V, T, check_mesh):
+        """The opt-in report on the mesh that is written (mesh.check): one line."""
+        if not check_mesh:
+            return
+        c = mesh.check(V, T, device=V.device)
+        yes = lambda b: "yes" if b else "no"  # noqa: E731
+        print(f"[{tag}] Mesh check: {c['vertices']} vertices, {c['triangles']} triangles, {c['boundary_edges']} "
+              f"boundary edges, {c['non_manifold_edges']} non-manifold edges, {c['non_manifold_vertices']} "
+              f"non-manifold vertices, orientable {yes(c['orientable'])}, watertight {yes(c['watertight'])}, "
+              f"area {c['area']!r}" + ("" if c["volume"] is None else f", volume {c['volume']!r}"))
+
+    @staticmethod
     def reconstruct_stl(input_path, output_path, mode="watertight", params=None, *, budget_bytes=None,
                         tangent_planes=None, ball_pivoting=False, keep_largest_component=False,
                         min_component_triangles=None, simplify_voxel_size=None, vertex_colors=False,
-                        smooth_iterations=None, smooth_method="taubin", smooth_fixed_boundary=False):
+                        smooth_iterations=None, smooth_method="taubin", smooth_fixed_boundary=False,
+                        check_mesh=False, repair_mesh=False):
         if not os.path.exists(input_path):
             raise FileNotFoundError(f"Input file not found: {input_path}")
         ProcessingLogic._check_smooth_method(smooth_method)
@@ -305,10 +351,12 @@ class ProcessingLogic:
             raise ValueError(f"Unknown mode: {mode}")
         V, T = ProcessingLogic._clean_mesh("Recon", V, T, keep_largest_component, min_component_triangles,
                                            simplify_voxel_size)
+        V, T = ProcessingLogic._repair_mesh("Recon", V, T, repair_mesh)
         if len(V) == 0:
             raise ValueError("Generated mesh is empty.")
         V = ProcessingLogic._smooth_mesh("Recon", V, T, smooth_iterations, smooth_method, smooth_fixed_boundary)
         colors = ProcessingLogic._vertex_colors("Recon", output_path, P, C, V, avg_dist) if vertex_colors else None
+        ProcessingLogic._check_mesh("Recon", V, T, check_mesh)
         print("[Recon] Computing normals and saving...")
         mesh.write_triangle_mesh(output_path, V, T, colors=colors)
         print(f"[Recon] Saved STL to {output_path}")
@@ -317,7 +365,7 @@ class ProcessingLogic:
     def mesh_360(input_path, output_path, depth=10, density_trim=0.01, orientation_mode="tangent", *,
                  budget_bytes=None, tangent_planes=None, keep_largest_component=False, min_component_triangles=None,
                  simplify_voxel_size=None, vertex_colors=False, smooth_iterations=None, smooth_method="taubin",
-                 smooth_fixed_boundary=False):
+                 smooth_fixed_boundary=False, check_mesh=False, repair_mesh=False):
         if not os.path.exists(input_path):
             raise FileNotFoundError(f"Input file not found: {input_path}")
         ProcessingLogic._check_smooth_method(smooth_method)
@@ -357,8 +405,10 @@ class ProcessingLogic:
             print("[360 Mesh] Density trim is 0.0 -> Keeping watertight result.")
         V, T = ProcessingLogic._clean_mesh("360 Mesh", V, T, keep_largest_component, min_component_triangles,
                                            simplify_voxel_size)
+        V, T = ProcessingLogic._repair_mesh("360 Mesh", V, T, repair_mesh)
         V = ProcessingLogic._smooth_mesh("360 Mesh", V, T, smooth_iterations, smooth_method, smooth_fixed_boundary)
         colors = ProcessingLogic._vertex_colors("360 Mesh", output_path, P, C, V) if vertex_colors else None
+        ProcessingLogic._check_mesh("360 Mesh", V, T, check_mesh)
         mesh.write_triangle_mesh(output_path, V, T, colors=colors)
         print(f"[360 Mesh] Saved to {output_path}")
 
