@@ -801,6 +801,49 @@ int sl_mesh_remove_duplicated_triangles(sl_ctx* ctx, const int32_t* triangles, i
                                         int64_t n_vertices, int32_t* out_triangles, int64_t* out_n_triangles,
                                         void* stream);
 
+/* ---- mesh hole filling (csrc/slmeshfill.inl, which states the definitions) ----
+ * The boundary components of a mesh and caps for the ones that are plain loops;
+ * definitions of this library's own (Open3D's tensor fill_holes is unpinned),
+ * exact against tests/meshfill_oracle.py and independent of any traversal or
+ * atomic order.  Inputs, limits and the index pass as for the mesh checks; a
+ * non-finite vertex is SL_EINVAL.  Blocking on `stream`; scratch from the
+ * merge stage's pool.
+ *   A boundary side is a side a->b whose edge has that one side (m = 1).  Sides
+ *   that share an end vertex are one component; its label is its smallest
+ *   vertex, its size its number of sides, its extent the diagonal of the box of
+ *   its vertices.  A vertex is simple iff one boundary side leaves and one
+ *   enters it; a component all of whose vertices are simple is a simple loop.
+ *   A simple loop is filled iff 3 <= size <= 2^22, size <= max_hole_edges and
+ *   extent <= hole_size (a negative limit: none; hole_size is inclusive): a
+ *   loop a->b->c->a of three sides, a the label, gets the triangle (a, c, b); a
+ *   longer one gets one new vertex at its centroid (64-bit fixed-point sums)
+ *   and the triangle (b, a, centre) per side a->b.
+ *   counts (host, int64 [8]), of both calls: 0 components, 1 simple loops,
+ *   2 filled loops, 3 skipped components that are not simple, 4 simple loops not
+ *   filled (over a limit, or fewer than three sides), 5 new vertices, 6 new
+ *   triangles, 7 boundary sides of the input.  sl_mesh_boundary_loops counts
+ *   what a fill without limits would do.
+ *   sl_mesh_boundary_loops   one row per component in ascending label ->
+ *       out_label int32, out_size int64, out_simple uint8, out_extent f64 (NULL
+ *       when vertices is NULL), device, room for counts[0] rows; with all four
+ *       NULL only the counts are computed, which is how a caller sizes them.
+ *   sl_mesh_fill_holes   out_vertices f64 [n_vertices + counts[5]][3]: the old
+ *       vertices, then the centroids in ascending label; out_triangles int32
+ *       [n_triangles + counts[6]][3]: the old triangles, then the new ones in
+ *       ascending from-vertex a (the triangle of a three-sided loop at its
+ *       label).  Room for n_vertices + components and n_triangles + boundary
+ *       sides rows always suffices; with both NULL only the counts are computed.
+ *   sl_mesh_fill_stats   the calling thread's last call of either: host
+ *       milliseconds per stage (side keys, sort, boundary sides, unions, per-loop
+ *       sums, caps or rows; stage_ms[capacity], zero-filled) -- a measurement aid. */
+int sl_mesh_boundary_loops(sl_ctx* ctx, const int32_t* triangles, int64_t n_triangles, const double* vertices,
+                           int64_t n_vertices, int32_t* out_label, int64_t* out_size, uint8_t* out_simple,
+                           double* out_extent, int64_t* counts, void* stream);
+int sl_mesh_fill_holes(sl_ctx* ctx, const double* vertices, int64_t n_vertices, const int32_t* triangles,
+                       int64_t n_triangles, int64_t max_hole_edges, double hole_size, double* out_vertices,
+                       int32_t* out_triangles, int64_t* counts, void* stream);
+int sl_mesh_fill_stats(double* stage_ms, int capacity);
+
 /* ---- consistent tangent-plane normal orientation (processing.py:201, :282) ----
  * orient_normals_consistent_tangent_plane restated on the kNN graph alone
  * (csrc/slorient.inl; tests/orient_oracle.py is the CPU restatement, bit for

@@ -59,6 +59,7 @@ EXPORTS = ("sl_abi_version", "sl_ctx_create", "sl_ctx_destroy", "sl_ctx_last_err
            "sl_mesh_adjacency", "sl_mesh_smooth", "sl_mesh_smooth_stats",
            "sl_mesh_check", "sl_mesh_check_stats", "sl_mesh_measure", "sl_mesh_remove_degenerate",
            "sl_mesh_remove_duplicated_triangles",
+           "sl_mesh_boundary_loops", "sl_mesh_fill_holes", "sl_mesh_fill_stats",
            "sl_information_matrix", "sl_pose_graph_optimize",
            "sl_radius_count", "sl_cluster_dbscan", "sl_cluster_dbscan_stats", "sl_nearest_neighbor_distance",
            "sl_ball_pivot_max_neighbours", "sl_ball_pivot_candidates", "sl_ball_pivot_candidates_stats",
@@ -158,6 +159,10 @@ _SIGS = {
                                ctypes.POINTER(ctypes.c_double), _vp]),
     "sl_mesh_remove_degenerate": (_i32, [_vp, _vp, _i64, _i64, _vp, ctypes.POINTER(_i64), _vp]),
     "sl_mesh_remove_duplicated_triangles": (_i32, [_vp, _vp, _i64, _i64, _vp, ctypes.POINTER(_i64), _vp]),
+    "sl_mesh_boundary_loops": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, ctypes.POINTER(_i64), _vp]),
+    "sl_mesh_fill_holes": (_i32, [_vp, _vp, _i64, _vp, _i64, _i64, ctypes.c_double, _vp, _vp, ctypes.POINTER(_i64),
+                                  _vp]),
+    "sl_mesh_fill_stats": (_i32, [ctypes.POINTER(ctypes.c_double), _i32]),
     "sl_orient_normals_mst": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, ctypes.POINTER(_i64),
                                      ctypes.POINTER(_i64), _vp]),
     "sl_orient_normals_mst_stats": (_i32, [ctypes.POINTER(_i32), ctypes.POINTER(_i32), _i32]),

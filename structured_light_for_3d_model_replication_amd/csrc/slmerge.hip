@@ -2303,3 +2303,5 @@ int sl_merge_pool_poison(int byte, int64_t* poisoned_bytes) {
 // mesh checks: edge and vertex manifoldness, orientability and orient_triangles, area and volume, degenerate and
 // duplicated triangles
 #include "slmeshcheck.inl"
+// mesh hole filling: boundary components, simple loops, triangle and centroid-fan caps
+#include "slmeshfill.inl"

@@ -112,56 +112,16 @@ enum { kUnique, kBoundary, kNonManifold, kInconsistent, kDegenerate, kOdd, kCoun
 thread_local double tls_ms[7];  // side keys, sort, classify + edge list, corners, parity unions, flips, measures
 
 using prim::require_finite, prim::require_indices;
-
-// dst += the lanes of the wave with p set: one atomic per wave.  Called by all lanes of the wave together.
-__device__ __forceinline__ void wave_add(unsigned long long* dst, bool p) {
-  const unsigned long long m = __ballot(p);
-  if (m && (threadIdx.x & 63) == __ffsll(m) - 1) atomicAdd(dst, static_cast<unsigned long long>(__popcll(m)));
-}
+using prim::wave_add, prim::Side, prim::side_of, prim::k_mk_sides, prim::bad_sizes;  // the boundary loops use them too
 
 __device__ __forceinline__ bool degenerate(const int32_t* tris, int64_t t) {
   const int32_t a = tris[3 * t], b = tris[3 * t + 1], c = tris[3 * t + 2];
   return a == b || b == c || c == a;
 }
 
-struct Side {
-  uint32_t t, k, from, to;
-};
-// the side a sorted value 3 t + k names
-__device__ __forceinline__ Side side_of(const int32_t* tris, uint32_t val) {
-  Side s;
-  s.t = val / 3u;
-  s.k = val - 3u * s.t;
-  s.from = static_cast<uint32_t>(tris[val]);
-  s.to = static_cast<uint32_t>(tris[s.k == 2u ? val - 2u : val + 1u]);
-  return s;
-}
 // the corner of side s at vertex v (one of its two ends; they differ)
 __device__ __forceinline__ uint32_t corner_at(const Side& s, uint32_t v) {
   return s.from == v ? 3u * s.t + s.k : 3u * s.t + (s.k == 2u ? 0u : s.k + 1u);
-}
-
-// Three (key, 3 t + k) pairs per triangle; the corner parents and the parity words start as roots.
-__global__ __launch_bounds__(kT) void k_mk_sides(const int32_t* tris, int64_t n_t, uint64_t n_v, uint64_t* keys,
-                                                 uint32_t* vals, uint32_t* parent, uint32_t* word,
-                                                 unsigned long long* cnt) {
-  const int64_t t = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
-  const bool live = t < n_t;
-  bool deg = false;
-  if (live) {
-    const uint64_t a = static_cast<uint64_t>(tris[3 * t]), b = static_cast<uint64_t>(tris[3 * t + 1]),
-                   c = static_cast<uint64_t>(tris[3 * t + 2]);
-    keys[3 * t] = a < b ? a * n_v + b : b * n_v + a;
-    keys[3 * t + 1] = b < c ? b * n_v + c : c * n_v + b;
-    keys[3 * t + 2] = c < a ? c * n_v + a : a * n_v + c;
-    const uint32_t v = static_cast<uint32_t>(3 * t);
-    vals[3 * t] = parent[3 * t] = v;
-    vals[3 * t + 1] = parent[3 * t + 1] = v + 1u;
-    vals[3 * t + 2] = parent[3 * t + 2] = v + 2u;
-    word[t] = static_cast<uint32_t>(t) << 1;
-    deg = a == b || b == c || c == a;
-  }
-  wave_add(cnt + kDegenerate, deg);
 }
 
 // One thread per sorted position: a run's head classifies its edge.  flag (may be NULL): 1 at the heads that go
@@ -331,10 +291,6 @@ __global__ __launch_bounds__(kT) void k_mk_keep(const int32_t* tris, int64_t n_t
   if (t < n_t) keep[t] = degenerate(tris, t) ? 0u : 1u;
 }
 
-bool bad_sizes(int64_t n_v, int64_t n_t) {
-  return n_v < 0 || n_t < 0 || n_v >= (1ll << 31) || 3 * n_t >= (1ll << 32);
-}
-
 }  // namespace mck
 }  // namespace
 
@@ -369,7 +325,7 @@ int sl_mesh_check(sl_ctx* c, const int32_t* triangles, int64_t n_triangles, int6
   MTRY(c, cnt.alloc(kCounters));
   MTRY(c, hipMemsetAsync(cnt.p, 0, sizeof(unsigned long long) * kCounters, s));
   hipLaunchKernelGGL(k_mk_sides, dim3(blocks(n)), dim3(kT), 0, s, triangles, n, nv, keys.p, vals.p, parent.p, word.p,
-                     cnt.p);
+                     cnt.p + kDegenerate);
   MTRY(c, hipGetLastError());
   MTRY(c, clock.lap(&tls_ms[0]));
   r = radix_sort(c, keys.p, vals.p, n3, key_bits(nv * nv - 1), s);  // only the bits the keys have

@@ -261,5 +261,60 @@ __global__ __launch_bounds__(kT) void k_sc_heads(const uint32_t* tri, const uint
   head[j] = first ? 1u : 0u;
 }
 
+// ------------------------------------------------------ triangle sides ----
+// (sl_mesh_check's and the boundary loops' one sort: csrc/slmeshcheck.inl's header states the keys)
+// dst += the lanes of the wave with p set: one atomic per wave.  Called by all lanes of the wave together.
+__device__ __forceinline__ void wave_add(unsigned long long* dst, bool p) {
+  const unsigned long long m = __ballot(p);
+  if (m && (threadIdx.x & 63) == __ffsll(m) - 1) atomicAdd(dst, static_cast<unsigned long long>(__popcll(m)));
+}
+
+struct Side {
+  uint32_t t, k, from, to;
+};
+// the side a sorted value 3 t + k names
+__device__ __forceinline__ Side side_of(const int32_t* tris, uint32_t val) {
+  Side s;
+  s.t = val / 3u;
+  s.k = val - 3u * s.t;
+  s.from = static_cast<uint32_t>(tris[val]);
+  s.to = static_cast<uint32_t>(tris[s.k == 2u ? val - 2u : val + 1u]);
+  return s;
+}
+
+// Three (key, 3 t + k) pairs per triangle.  Optional (NULL: skipped): the corner parents and the parity words start
+// as roots, *n_degenerate += the triangles with two equal indices.
+__global__ __launch_bounds__(kT) void k_mk_sides(const int32_t* tris, int64_t n_t, uint64_t n_v, uint64_t* keys,
+                                                 uint32_t* vals, uint32_t* parent, uint32_t* word,
+                                                 unsigned long long* n_degenerate) {
+  const int64_t t = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
+  const bool live = t < n_t;
+  bool deg = false;
+  if (live) {
+    const uint64_t a = static_cast<uint64_t>(tris[3 * t]), b = static_cast<uint64_t>(tris[3 * t + 1]),
+                   c = static_cast<uint64_t>(tris[3 * t + 2]);
+    keys[3 * t] = a < b ? a * n_v + b : b * n_v + a;
+    keys[3 * t + 1] = b < c ? b * n_v + c : c * n_v + b;
+    keys[3 * t + 2] = c < a ? c * n_v + a : a * n_v + c;
+    const uint32_t v = static_cast<uint32_t>(3 * t);
+    vals[3 * t] = v;
+    vals[3 * t + 1] = v + 1u;
+    vals[3 * t + 2] = v + 2u;
+    if (parent) {
+      parent[3 * t] = v;
+      parent[3 * t + 1] = v + 1u;
+      parent[3 * t + 2] = v + 2u;
+    }
+    if (word) word[t] = static_cast<uint32_t>(t) << 1;
+    deg = a == b || b == c || c == a;
+  }
+  if (n_degenerate) wave_add(n_degenerate, deg);
+}
+
+// the limits of the side keys and of the values 3 t + k
+bool bad_sizes(int64_t n_v, int64_t n_t) {
+  return n_v < 0 || n_t < 0 || n_v >= (1ll << 31) || 3 * n_t >= (1ll << 32);
+}
+
 }  // namespace prim
 }  // namespace

@@ -64,6 +64,13 @@ the definitions; exact against tests/meshcheck_oracle.py).  Open3D's
 ``remove_duplicated_triangles``.  The drop-ins report and repair when asked to
 (``check_mesh``, ``repair_mesh``).
 
+``fill_holes`` closes the holes ``check`` reports: ``boundary_loops`` lists the
+boundary components (sides that share a vertex), and every one that is a plain
+cycle within the limits gets a triangle or a fan about its centroid, an
+order-free fixed-point mean (csrc/slmeshfill.inl states the definitions; exact
+against tests/meshfill_oracle.py).  The drop-ins apply it when asked to
+(``fill_holes``, ``fill_hole_size``, ``fill_max_edges``).
+
 Open3D's Poisson is the adaptive-octree variant and is not installed here:
 parity with Open3D is unpinned, and tests/mesh_oracle.py is the CPU restatement
 the tests check against -- bit for bit for every stage except the solve.
@@ -763,6 +770,87 @@ def remove_duplicated_triangles(vertices, triangles, *, n_vertices=None, device=
     ``simplify_vertex_clustering``'s rule.  Deviation: the kept triangle is
     stored as it was given (Open3D stores the rotated form)."""
     return _remove("sl_mesh_remove_duplicated_triangles", vertices, triangles, n_vertices, device)
+
+
+_FILL_COUNTS = ("components", "simple_loops", "filled", "skipped_not_simple", "skipped_by_limit", "new_vertices",
+                "new_triangles", "boundary_sides")
+
+
+def boundary_loops(vertices, triangles, *, n_vertices=None, device=None) -> dict:
+    """The boundary components of a mesh (csrc/slmeshfill.inl states the
+    definitions; exact against tests/meshfill_oracle.py) -> a dict of device
+    tensors with one row per component, in ascending label: "label" int32 (the
+    component's smallest vertex), "size" int64 (its boundary sides), "simple"
+    bool (every vertex has one side leaving and one entering: one cycle, which
+    ``fill_holes`` can close), and "extent" f64 (the diagonal of the box of its
+    vertices) when ``vertices`` is given.  A boundary side is a triangle side
+    whose edge no other side shares; sides that share an end vertex are one
+    component.  ``vertices`` may be None when ``n_vertices`` is given."""
+    eng, Vx, T, nv = _check_args(vertices, triangles, n_vertices, device)
+    dev, t = eng.device, len(T)
+    counts = (ctypes.c_int64 * 8)()
+    args = (_ptr(T) if t else None, t, _ptr(Vx) if Vx is not None and nv else None, nv)
+    _call(eng, "sl_mesh_boundary_loops", *args, None, None, None, None, counts)      # the number of rows
+    rows = counts[0]
+    out = {"label": torch.empty(rows, dtype=torch.int32, device=dev),
+           "size": torch.empty(rows, dtype=torch.int64, device=dev),
+           "simple": torch.empty(rows, dtype=torch.uint8, device=dev)}
+    if Vx is not None:
+        out["extent"] = torch.empty(rows, dtype=torch.float64, device=dev)
+    if rows:
+        _call(eng, "sl_mesh_boundary_loops", *args, _ptr(out["label"]), _ptr(out["size"]), _ptr(out["simple"]),
+              _ptr(out.get("extent")), counts)
+    out["simple"] = out["simple"].to(torch.bool)
+    return out
+
+
+def fill_holes(vertices, triangles, *, hole_size=None, max_hole_edges=None, info: bool = False, device=None):
+    """Close the holes of a mesh that are plain loops -> (vertices f64 [V', 3],
+    triangles int32 [T', 3]) on the device, and with ``info`` the counts dict
+    too (csrc/slmeshfill.inl states the definitions; exact against
+    tests/meshfill_oracle.py).  A simple loop (``boundary_loops``) of three
+    sides a -> b -> c -> a gets the triangle (a, c, b); a longer one gets one new
+    vertex at its centroid and the triangle (b, a, centre) per side a -> b, so
+    a consistently wound mesh stays consistent.  ``max_hole_edges`` and
+    ``hole_size`` (the largest extent, inclusive) leave larger loops open.
+    Components that are not simple loops -- holes that touch in a vertex, the
+    open fans at a non-manifold vertex -- are skipped and counted.  The old
+    vertices and triangles are a prefix of the results; the new vertices follow
+    in ascending label, the new triangles in ascending from-vertex.  Counts:
+    "components", "simple_loops", "filled", "skipped_not_simple",
+    "skipped_by_limit", "new_vertices", "new_triangles", "boundary_sides".
+    Deviations: centroid fans, not a minimal-area triangulation; parity with
+    Open3D's fill_holes is unpinned.  A negative or NaN limit raises ValueError.
+    The inputs are never modified."""
+    if hole_size is not None and not float(hole_size) >= 0.0:
+        raise ValueError("hole_size must be a number >= 0")
+    if max_hole_edges is not None and int(max_hole_edges) < 0:
+        raise ValueError("max_hole_edges must be >= 0")
+    eng, Vx, T, nv = _check_args(vertices, triangles, None, device)
+    dev, t = eng.device, len(T)
+    counts = (ctypes.c_int64 * 8)()
+    args = (_ptr(Vx) if nv else None, nv, _ptr(T) if t else None, t,
+            -1 if max_hole_edges is None else int(max_hole_edges), -1.0 if hole_size is None else float(hole_size))
+    _call(eng, "sl_mesh_fill_holes", *args, None, None, counts)                       # the sizes of the results
+    Vo = torch.empty((nv + counts[5], 3), dtype=torch.float64, device=dev)
+    To = torch.empty((t + counts[6], 3), dtype=torch.int32, device=dev)
+    if counts[6]:
+        _call(eng, "sl_mesh_fill_holes", *args, _ptr(Vo), _ptr(To), counts)
+    else:
+        Vo.copy_(Vx)
+        To.copy_(T)
+    return (Vo, To, dict(zip(_FILL_COUNTS, counts))) if info else (Vo, To)
+
+
+def fill_stats(*, device=None) -> dict:
+    """Host milliseconds per stage of this thread's last ``fill_holes`` or
+    ``boundary_loops`` call into the library (sl_mesh_fill_stats; a measurement
+    aid; both make two calls, the first of which only counts)."""
+    eng = _engine(device)
+    v = (ctypes.c_double * 6)()
+    _lib.check(eng._L.sl_mesh_fill_stats(v, 6), None, "sl_mesh_fill_stats")
+    return {"side_keys_ms": v[0], "sort_ms": v[1], "boundary_ms": v[2], "union_ms": v[3], "loops_ms": v[4],
+            "caps_ms": v[5]}
 
 
 def quantile(values, q: float) -> float:

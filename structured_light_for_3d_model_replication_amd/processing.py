@@ -64,6 +64,13 @@ errors, and runs them on the GPU through ``merge`` (libslgpu.so):
   ``check_mesh`` reports on the mesh that is written, just before the writer: one ``Mesh check:`` line of
   ``mesh.check``'s counts -- vertices, triangles, boundary and non-manifold edges, non-manifold vertices,
   orientable, watertight, the area, and the volume when the mesh is watertight.  With both off nothing changes.
+  Three more, ``fill_holes=False``, ``fill_hole_size=None`` and ``fill_max_edges=None`` (csrc/slmeshfill.inl).
+  ``fill_holes`` runs after the repair, whose windings the caps continue, and before the smoothing, which relaxes
+  the flat fans: ``mesh.fill_holes`` closes every boundary loop within the two limits (the largest extent of a
+  loop's box, inclusive, and the most sides) with a triangle or a fan about its centroid; one ``Fill holes:`` line
+  of the loops filled, the components that are not simple loops and the loops over a limit, both left open, and
+  the vertices and triangles added.  The density trim opens such loops, so the default output is not watertight;
+  the reference's answer is not to trim.  Off by default: nothing changes.
 
 Without Open3D, "a point cloud object" is a ``Cloud(points, colors)`` of
 device tensors (f64 [N, 3], BGR u8 [N, 3] or None).  It is accepted wherever
@@ -290,6 +297,19 @@ class ProcessingLogic:
         return V, T
 
     @staticmethod
+    def _fill_holes(tag, V, T, fill_holes, fill_hole_size, fill_max_edges):
+        """The opt-in hole filling of the drop-ins' mesh (mesh.fill_holes, csrc/slmeshfill.inl): the boundary loops
+        within the two limits get a triangle or a centroid fan.  One line with the counts."""
+        if not fill_holes:
+            return V, T
+        V, T, c = mesh.fill_holes(V, T, hole_size=fill_hole_size, max_hole_edges=fill_max_edges, info=True,
+                                  device=V.device)
+        print(f"[{tag}] Fill holes: {c['filled']} of {c['simple_loops']} loops filled ({c['skipped_not_simple']} not "
+              f"simple, {c['skipped_by_limit']} over the limit), +{c['new_vertices']} vertices, "
+              f"+{c['new_triangles']} triangles")
+        return V, T
+
+    @staticmethod
     def _check_mesh(tag, V, T, check_mesh):
         """The opt-in report on the mesh that is written (mesh.check): one line."""
         if not check_mesh:
@@ -306,7 +326,8 @@ class ProcessingLogic:
                         tangent_planes=None, ball_pivoting=False, keep_largest_component=False,
                         min_component_triangles=None, simplify_voxel_size=None, vertex_colors=False,
                         smooth_iterations=None, smooth_method="taubin", smooth_fixed_boundary=False,
-                        check_mesh=False, repair_mesh=False):
+                        check_mesh=False, repair_mesh=False, fill_holes=False, fill_hole_size=None,
+                        fill_max_edges=None):
         if not os.path.exists(input_path):
             raise FileNotFoundError(f"Input file not found: {input_path}")
         ProcessingLogic._check_smooth_method(smooth_method)
@@ -352,6 +373,7 @@ class ProcessingLogic:
         V, T = ProcessingLogic._clean_mesh("Recon", V, T, keep_largest_component, min_component_triangles,
                                            simplify_voxel_size)
         V, T = ProcessingLogic._repair_mesh("Recon", V, T, repair_mesh)
+        V, T = ProcessingLogic._fill_holes("Recon", V, T, fill_holes, fill_hole_size, fill_max_edges)
         if len(V) == 0:
             raise ValueError("Generated mesh is empty.")
         V = ProcessingLogic._smooth_mesh("Recon", V, T, smooth_iterations, smooth_method, smooth_fixed_boundary)
@@ -365,7 +387,8 @@ class ProcessingLogic:
     def mesh_360(input_path, output_path, depth=10, density_trim=0.01, orientation_mode="tangent", *,
                  budget_bytes=None, tangent_planes=None, keep_largest_component=False, min_component_triangles=None,
                  simplify_voxel_size=None, vertex_colors=False, smooth_iterations=None, smooth_method="taubin",
-                 smooth_fixed_boundary=False, check_mesh=False, repair_mesh=False):
+                 smooth_fixed_boundary=False, check_mesh=False, repair_mesh=False, fill_holes=False,
+                 fill_hole_size=None, fill_max_edges=None):
         if not os.path.exists(input_path):
             raise FileNotFoundError(f"Input file not found: {input_path}")
         ProcessingLogic._check_smooth_method(smooth_method)
@@ -406,6 +429,7 @@ class ProcessingLogic:
         V, T = ProcessingLogic._clean_mesh("360 Mesh", V, T, keep_largest_component, min_component_triangles,
                                            simplify_voxel_size)
         V, T = ProcessingLogic._repair_mesh("360 Mesh", V, T, repair_mesh)
+        V, T = ProcessingLogic._fill_holes("360 Mesh", V, T, fill_holes, fill_hole_size, fill_max_edges)
         V = ProcessingLogic._smooth_mesh("360 Mesh", V, T, smooth_iterations, smooth_method, smooth_fixed_boundary)
         colors = ProcessingLogic._vertex_colors("360 Mesh", output_path, P, C, V) if vertex_colors else None
         ProcessingLogic._check_mesh("360 Mesh", V, T, check_mesh)
