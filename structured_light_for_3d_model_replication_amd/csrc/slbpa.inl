@@ -383,10 +383,7 @@ int sl_ball_pivot_candidates(sl_ctx* c, const double* xyz, const double* normals
 }
 
 int sl_ball_pivot_candidates_stats(double* stats, int capacity) {
-  using namespace bpa;
-  if (capacity < 0 || (capacity && !stats)) return SL_EINVAL;
-  for (int i = 0; i < capacity; ++i) stats[i] = i < 7 ? tls_stats[i] : 0.0;
-  return SL_OK;
+  return prim::copy_stats(bpa::tls_stats, stats, capacity);
 }
 
 }  // extern "C"

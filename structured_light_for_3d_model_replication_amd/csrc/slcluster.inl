@@ -199,11 +199,7 @@ __global__ __launch_bounds__(kT) void k_clu_roots(const uint32_t* parent, const 
                                                   const uint32_t* sidx, int64_t n, uint32_t* root, uint32_t* low) {
   const int64_t t = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
   const bool core = t < n && scnt[t] >= min_points;
-  uint32_t x = kNone;
-  if (core) {
-    x = static_cast<uint32_t>(t);
-    for (uint32_t p = parent[x]; p != x; p = parent[x]) x = p;  // strictly decreasing
-  }
+  const uint32_t x = core ? prim::root_of(parent, static_cast<uint32_t>(t)) : kNone;
   if (t < n) root[t] = x;
   // neighbours in position mostly share a root: one atomic per wave and root, not one per point (a
   // cluster of millions otherwise queues them all on one word).  Every lane of the wave calls.
@@ -333,10 +329,7 @@ int sl_cluster_dbscan(sl_ctx* c, const double* xyz, int64_t n, double eps, int m
 }
 
 int sl_cluster_dbscan_stats(double* stage_ms, int capacity) {
-  using namespace clu;
-  if (capacity < 0 || (capacity && !stage_ms)) return SL_EINVAL;
-  for (int i = 0; i < capacity; ++i) stage_ms[i] = i < 5 ? tls_ms[i] : 0.0;
-  return SL_OK;
+  return prim::copy_stats(clu::tls_ms, stage_ms, capacity);
 }
 
 int sl_nearest_neighbor_distance(sl_ctx* c, const double* xyz, int64_t n, double* out, void* stream) {

@@ -1,7 +1,7 @@
 // libslgpu.so, part 2m -- mesh checks, included at the end of slmerge.hip (one
 // translation unit: it uses that file's scratch pool, radix and triple sorts,
-// scan and row compaction, slprim.inl's union-find, rotated triples, input
-// checks and stage clock, and the C entry point sl_ordered_sum).  Open3D users
+// scan and row compaction, slprim.inl's side table, union-find, rotated triples,
+// triangle area, input checks and stage clock, and the C entry point sl_ordered_sum).  Open3D users
 // ask a TriangleMesh is_edge_manifold, is_vertex_manifold, is_orientable,
 // is_watertight, get_non_manifold_edges, get_non_manifold_vertices,
 // orient_triangles, get_surface_area, get_volume, remove_degenerate_triangles
@@ -11,12 +11,12 @@
 // check against, exactly.
 //
 // Input: triangles int32 [T][3], n_vertices V, vertices f64 [V][3] for the
-// measures; V < 2^31, 3 T < 2^32 (slmeshclean.inl's limits).  prim::require_indices
+// measures; V < 2^31, 3 T < 2^32 (prim::bad_sizes).  prim::require_indices
 // reads every index before anything is indexed: one outside 0 .. V-1 is
 // SL_EINDEX ("... triangle index out of range"), never a load.
 //
 //   sides     (a, b, c) has the sides a->b, b->c, c->a.  A side's key is min V +
-//             max (k_mc_edges' key), its direction bit is from < to.  A triangle
+//             max (slprim.inl's side table), its direction bit is from < to.  A triangle
 //             with two equal indices is DEGENERATE; it still gives its three
 //             sides to the edge counts, as Open3D's edges_to_triangles map does:
 //             (a, a, b) gives {a, a} once and {a, b} twice.
@@ -48,8 +48,8 @@
 //   watertight  edge-manifold without boundary, vertex-manifold, no inconsistent
 //             edge, as given (no flips are searched).  DEVIATION: Open3D also
 //             tests self-intersection (an O(T^2) pair loop); that is not built.
-//   measures  f64, uncontracted.  A_t = 0.5 sqrt((n0 n0 + n1 n1) + n2 n2), n =
-//             (v1 - v0) x (v2 - v0) (slmeshclean.inl's cluster areas use the same).
+//   measures  f64, uncontracted.  A_t = prim::tri_area(v0, v1, v2), half the length
+//             of (v1 - v0) x (v2 - v0).
 //             W_t = ((x0 c0 + y0 c1) + z0 c2) / 6.0, c = v1 x v2, c0 = y1 z2 - z1
 //             y2, c1 = z1 x2 - x1 z2, c2 = x1 y2 - y1 x2.  Area and signed volume
 //             are the ordered sums (slplane.inl) of A_t and W_t in triangle order.
@@ -61,12 +61,11 @@
 //             every rotated triple is kept, in input order, stored AS GIVEN
 //             (DEVIATION: Open3D stores the rotated form).
 //
-// One sort per sl_mesh_check.  k_mk_sides writes three (key, 3 t + k) pairs per
-// triangle; radix_sort orders them over the bits V V - 1 has; everything else
-// looks at run neighbours.  The triangle, side and direction bit of a sorted
-// entry come back from its value by one gather.
-//   k_mk_classify   a run's head looks at i - 1, i + 1 and i + 2: enough to tell
-//             m = 1, 2 and >= 3.  Counters are integer atomics, one per wave and
+// One sort per sl_mesh_check: prim::sort_sides' table of three (key, 3 t + k)
+// pairs per triangle; everything else looks at run neighbours.  The triangle,
+// side and direction bit of a sorted entry come back from its value by one gather.
+//   k_mk_classify   a run's head asks prim::run_sides (i - 1, i + 1 and i + 2) for
+//             m = 1, 2 or >= 3.  Counters are integer atomics, one per wave and
 //             counter, by ballot.  The edge list: flags, scan_flags, a gather.
 //   k_mk_corner_union   entry i unites its two corners with those of the nearest
 //             earlier entry of its run whose triangle is not degenerate (the
@@ -112,7 +111,7 @@ enum { kUnique, kBoundary, kNonManifold, kInconsistent, kDegenerate, kOdd, kCoun
 thread_local double tls_ms[7];  // side keys, sort, classify + edge list, corners, parity unions, flips, measures
 
 using prim::require_finite, prim::require_indices;
-using prim::wave_add, prim::Side, prim::side_of, prim::k_mk_sides, prim::bad_sizes;  // the boundary loops use them too
+using prim::wave_add, prim::Side, prim::side_of, prim::bad_sizes;
 
 __device__ __forceinline__ bool degenerate(const int32_t* tris, int64_t t) {
   const int32_t a = tris[3 * t], b = tris[3 * t + 1], c = tris[3 * t + 2];
@@ -131,25 +130,19 @@ __global__ __launch_bounds__(kT) void k_mk_classify(const uint64_t* keys, const 
                                                     uint32_t* flag) {
   const int64_t i = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
   const bool live = i < n3;
-  bool head = false, one = false, many = false, odd = false;
+  int m = 0;  // the sides of the run that starts here
+  bool odd = false;
   if (live) {
-    const uint64_t k = keys[i];
-    head = i == 0 || keys[i - 1] != k;
-    if (head) {
-      const bool n1 = i + 1 < n3 && keys[i + 1] == k;
-      const bool n2 = n1 && i + 2 < n3 && keys[i + 2] == k;
-      one = !n1;
-      many = n2;
-      if (n1 && !n2) {
-        const Side a = side_of(tris, vals[i]), b = side_of(tris, vals[i + 1]);
-        odd = (a.from < a.to) == (b.from < b.to);
-      }
+    m = prim::run_sides(keys, i, n3);
+    if (m == 2) {
+      const Side a = side_of(tris, vals[i]), b = side_of(tris, vals[i + 1]);
+      odd = (a.from < a.to) == (b.from < b.to);
     }
-    if (flag) flag[i] = (many || (one && !allow_boundary)) ? 1u : 0u;
+    if (flag) flag[i] = (m == 3 || (m == 1 && !allow_boundary)) ? 1u : 0u;
   }
-  wave_add(cnt + kUnique, head);
-  wave_add(cnt + kBoundary, one);
-  wave_add(cnt + kNonManifold, many);
+  wave_add(cnt + kUnique, m != 0);
+  wave_add(cnt + kBoundary, m == 1);
+  wave_add(cnt + kNonManifold, m == 3);
   wave_add(cnt + kInconsistent, odd);
 }
 
@@ -238,15 +231,13 @@ __device__ __forceinline__ void unite_parity(uint32_t* word, uint32_t a, uint32_
   }
 }
 
-// One thread per run of exactly two sides (at its second entry).
+// One thread per run of exactly two sides (at its first entry).
 __global__ __launch_bounds__(kT) void k_mk_parity_union(const uint64_t* keys, const uint32_t* vals,
                                                         const int32_t* tris, int64_t n3, uint32_t* word,
                                                         unsigned long long* cnt) {
   const int64_t i = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
-  if (i < 1 || i >= n3) return;
-  const uint64_t k = keys[i];
-  if (keys[i - 1] != k || (i >= 2 && keys[i - 2] == k) || (i + 1 < n3 && keys[i + 1] == k)) return;
-  const Side a = side_of(tris, vals[i - 1]), b = side_of(tris, vals[i]);
+  if (i >= n3 || prim::run_sides(keys, i, n3) != 2) return;
+  const Side a = side_of(tris, vals[i]), b = side_of(tris, vals[i + 1]);
   const uint32_t rel = (a.from < a.to) == (b.from < b.to) ? 1u : 0u;
   if (a.t == b.t || a.from == a.to) {  // one triangle, or two loops {v, v} (rel = 1): no flip changes the pair
     if (rel) atomicOr(cnt + kOdd, 1ull);
@@ -278,10 +269,7 @@ __global__ __launch_bounds__(kT) void k_mk_measure(const double* verts, const in
   if (t >= n_t) return;
   const prim::D3 p0 = prim::ld3(verts, tris[3 * t]), p1 = prim::ld3(verts, tris[3 * t + 1]),
                  p2 = prim::ld3(verts, tris[3 * t + 2]);
-  const double e10 = p1.x - p0.x, e11 = p1.y - p0.y, e12 = p1.z - p0.z;
-  const double e20 = p2.x - p0.x, e21 = p2.y - p0.y, e22 = p2.z - p0.z;
-  const double n0 = e11 * e22 - e12 * e21, n1 = e12 * e20 - e10 * e22, n2 = e10 * e21 - e11 * e20;
-  area[t] = 0.5 * sqrt((n0 * n0 + n1 * n1) + n2 * n2);
+  area[t] = prim::tri_area(p0, p1, p2);
   const double c0 = p1.y * p2.z - p1.z * p2.y, c1 = p1.z * p2.x - p1.x * p2.z, c2 = p1.x * p2.y - p1.y * p2.x;
   vol[t] = ((p0.x * c0 + p0.y * c1) + p0.z * c2) / 6.0;
 }
@@ -315,36 +303,29 @@ int sl_mesh_check(sl_ctx* c, const int32_t* triangles, int64_t n_triangles, int6
   if (r) return r;
   prim::StageClock clock(s);
   const uint64_t nv = static_cast<uint64_t>(n_vertices);
-  DBuf<uint64_t> keys;
-  DBuf<uint32_t> vals, parent, word;
+  prim::SideTable S;
+  DBuf<uint32_t> parent, word;
   DBuf<unsigned long long> cnt;
-  MTRY(c, keys.alloc(n3));
-  MTRY(c, vals.alloc(n3));
   MTRY(c, parent.alloc(n3));
   MTRY(c, word.alloc(n));
   MTRY(c, cnt.alloc(kCounters));
   MTRY(c, hipMemsetAsync(cnt.p, 0, sizeof(unsigned long long) * kCounters, s));
-  hipLaunchKernelGGL(k_mk_sides, dim3(blocks(n)), dim3(kT), 0, s, triangles, n, nv, keys.p, vals.p, parent.p, word.p,
-                     cnt.p + kDegenerate);
-  MTRY(c, hipGetLastError());
-  MTRY(c, clock.lap(&tls_ms[0]));
-  r = radix_sort(c, keys.p, vals.p, n3, key_bits(nv * nv - 1), s);  // only the bits the keys have
+  r = prim::sort_sides(c, triangles, n, nv, S, parent.p, word.p, cnt.p + kDegenerate, clock, &tls_ms[0], &tls_ms[1], s);
   if (r) return r;
-  MTRY(c, clock.lap(&tls_ms[1]));
   {
     DBuf<uint32_t> flag, pos;
     if (edges) {
       MTRY(c, flag.alloc(n3));
       MTRY(c, pos.alloc(n3));
     }
-    hipLaunchKernelGGL(k_mk_classify, dim3(blocks(n3)), dim3(kT), 0, s, keys.p, vals.p, triangles, n3,
+    hipLaunchKernelGGL(k_mk_classify, dim3(blocks(n3)), dim3(kT), 0, s, S.keys.p, S.vals.p, triangles, n3,
                        allow_boundary_edges, cnt.p, flag.p);
     MTRY(c, hipGetLastError());
     if (edges) {
       int64_t rows = 0;
       r = scan_flags(c, flag.p, n3, pos.p, &rows, s);
       if (r) return r;
-      hipLaunchKernelGGL(k_mk_edge_list, dim3(blocks(n3)), dim3(kT), 0, s, keys.p, flag.p, pos.p, n3, nv, edges);
+      hipLaunchKernelGGL(k_mk_edge_list, dim3(blocks(n3)), dim3(kT), 0, s, S.keys.p, flag.p, pos.p, n3, nv, edges);
       MTRY(c, hipGetLastError());
     }
     MTRY(c, clock.lap(&tls_ms[2]));
@@ -355,7 +336,8 @@ int sl_mesh_check(sl_ctx* c, const int32_t* triangles, int64_t n_triangles, int6
     MTRY(c, flag.alloc(n_vertices));
     MTRY(c, pos.alloc(n_vertices));
     MTRY(c, hipMemsetAsync(nroots.p, 0, sizeof(uint32_t) * n_vertices, s));
-    hipLaunchKernelGGL(k_mk_corner_union, dim3(blocks(n3)), dim3(kT), 0, s, keys.p, vals.p, triangles, n3, parent.p);
+    hipLaunchKernelGGL(k_mk_corner_union, dim3(blocks(n3)), dim3(kT), 0, s, S.keys.p, S.vals.p, triangles, n3,
+                       parent.p);
     hipLaunchKernelGGL(k_mk_corner_roots, dim3(blocks(n3)), dim3(kT), 0, s, parent.p, triangles, n3, nroots.p);
     hipLaunchKernelGGL(k_mk_vertex_flags, dim3(blocks(n_vertices)), dim3(kT), 0, s, nroots.p, n_vertices, flag.p);
     MTRY(c, hipGetLastError());
@@ -368,7 +350,7 @@ int sl_mesh_check(sl_ctx* c, const int32_t* triangles, int64_t n_triangles, int6
     }
     MTRY(c, clock.lap(&tls_ms[3]));
   }
-  hipLaunchKernelGGL(k_mk_parity_union, dim3(blocks(n3)), dim3(kT), 0, s, keys.p, vals.p, triangles, n3, word.p,
+  hipLaunchKernelGGL(k_mk_parity_union, dim3(blocks(n3)), dim3(kT), 0, s, S.keys.p, S.vals.p, triangles, n3, word.p,
                      cnt.p);
   MTRY(c, hipGetLastError());
   unsigned long long h[kCounters];
@@ -391,10 +373,7 @@ int sl_mesh_check(sl_ctx* c, const int32_t* triangles, int64_t n_triangles, int6
 }
 
 int sl_mesh_check_stats(double* stage_ms, int capacity) {
-  using namespace mck;
-  if (capacity < 0 || (capacity && !stage_ms)) return SL_EINVAL;
-  for (int i = 0; i < capacity; ++i) stage_ms[i] = i < 7 ? tls_ms[i] : 0.0;
-  return SL_OK;
+  return prim::copy_stats(mck::tls_ms, stage_ms, capacity);
 }
 
 int sl_mesh_measure(sl_ctx* c, const double* vertices, int64_t n_vertices, const int32_t* triangles,

@@ -1,7 +1,8 @@
 // libslgpu.so, part 2i -- mesh clean-up after the density trim, included at the
 // end of slmerge.hip (one translation unit: it shares that file's scratch pool,
 // radix and triple sorts, scan, key runs, row compaction, bounds and voxel grid,
-// and slprim.inl's lock-free union-find, input checks and stage clock).  Open3D users clean a Poisson mesh with
+// and slprim.inl's side table, lock-free union-find, triangle area, input checks
+// and stage clock).  Open3D users clean a Poisson mesh with
 // TriangleMesh::ClusterConnectedTriangles + RemoveTrianglesByMask +
 // RemoveUnreferencedVertices and make it coarser with
 // SimplifyVertexClustering(voxel_size, Average).  They are restated here; Open3D
@@ -25,8 +26,8 @@
 //              loop (triangle indices ascending, breadth-first from the first
 //              unlabelled one) assigns;
 //     count    the cluster's triangles (int64);
-//     area     A_t = 0.5 sqrt((n0 n0 + n1 n1) + n2 n2), n = (v_b - v_a) x (v_c -
-//              v_a), f64, uncontracted.  A cluster's area is taken over its
+//     area     A_t = prim::tri_area(v_a, v_b, v_c): half the length of (v_b - v_a)
+//              x (v_c - v_a), f64, uncontracted.  A cluster's area is taken over its
 //              triangles in ascending index in blocks of kBlock = 64 consecutive
 //              members counted from its first member; a block is a left fold from
 //              0.0 and the block sums are a left fold from 0.0 (the kIcpBlock
@@ -55,10 +56,11 @@
 //              (Open3D: the order of an unordered_set).
 //     The result is in general not manifold: that is the algorithm.
 //
-// Components on the device.  k_mc_edges writes three (key, triangle) pairs per
-// triangle; radix_sort orders them over the bits V V - 1 has; one thread per
-// sorted position i > 0 with key[i] == key[i-1] unites value[i] and value[i-1]
-// (run neighbours suffice: the chain connects the whole run).  parent[] is
+// Components on the device.  prim::sort_sides leaves the sorted side table,
+// three (key, 3 t + k) pairs per triangle; one thread per sorted position i > 0
+// with key[i] == key[i-1] unites the triangles value / 3 of i and i - 1 (run
+// neighbours suffice: the chain connects the whole run; the two equal sides of
+// one degenerate triangle name the same triangle and are skipped).  parent[] is
 // indexed by triangle and starts as the identity.  The union-find is slprim.inl's,
 // and the argument in that file's header holds unchanged and is what keeps this
 // wait-free: a component's final root is its smallest triangle index whatever
@@ -86,34 +88,22 @@ constexpr int kBlock = 64;  // members per area block
 
 thread_local double tls_ms[6];  // edge keys, sort, union, flatten + rank, counts, areas of the last clustering
 
-using prim::require_finite, prim::require_indices;  // the latter: k_mc_check
+using prim::require_finite, prim::require_indices, prim::bad_sizes;  // require_indices: k_mc_check
 
-__global__ __launch_bounds__(kT) void k_mc_edges(const int32_t* tris, int64_t n_t, uint64_t n_v, uint64_t* keys,
-                                                 uint32_t* vals) {
-  const int64_t t = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
-  if (t >= n_t) return;
-  const uint64_t a = static_cast<uint64_t>(tris[3 * t]), b = static_cast<uint64_t>(tris[3 * t + 1]),
-                 c = static_cast<uint64_t>(tris[3 * t + 2]);
-  keys[3 * t] = a < b ? a * n_v + b : b * n_v + a;
-  keys[3 * t + 1] = b < c ? b * n_v + c : c * n_v + b;
-  keys[3 * t + 2] = c < a ? c * n_v + a : a * n_v + c;
-  vals[3 * t] = vals[3 * t + 1] = vals[3 * t + 2] = static_cast<uint32_t>(t);
-}
-
+// vals: 3 t + k of the sorted sides
 __global__ __launch_bounds__(kT) void k_mc_union(const uint64_t* keys, const uint32_t* vals, int64_t n3,
                                                  uint32_t* parent) {
   const int64_t i = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
   if (i < 1 || i >= n3 || keys[i] != keys[i - 1]) return;
-  const uint32_t a = vals[i], b = vals[i - 1];
+  const uint32_t a = vals[i] / 3u, b = vals[i - 1] / 3u;
   if (a != b) prim::unite(parent, a, b);
 }
 
-// After the unions (a kernel boundary: plain loads): root[t], and flag[t] = 1 for the roots.
+// After the unions: root[t], and flag[t] = 1 for the roots.
 __global__ __launch_bounds__(kT) void k_mc_roots(const uint32_t* parent, int64_t n_t, uint32_t* root, uint32_t* flag) {
   const int64_t t = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
   if (t >= n_t) return;
-  uint32_t x = static_cast<uint32_t>(t);
-  for (uint32_t p = parent[x]; p != x; p = parent[x]) x = p;  // strictly decreasing
+  const uint32_t x = prim::root_of(parent, static_cast<uint32_t>(t));
   root[t] = x;
   flag[t] = x == static_cast<uint32_t>(t) ? 1u : 0u;
 }
@@ -158,13 +148,8 @@ __global__ __launch_bounds__(kT) void k_mc_area(const double* verts, const int32
   const int64_t p = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
   if (p >= n_t) return;
   const int64_t t = order[p];
-  const int64_t a = tris[3 * t], b = tris[3 * t + 1], c = tris[3 * t + 2];
-  const double e10 = verts[3 * b] - verts[3 * a], e11 = verts[3 * b + 1] - verts[3 * a + 1],
-               e12 = verts[3 * b + 2] - verts[3 * a + 2];
-  const double e20 = verts[3 * c] - verts[3 * a], e21 = verts[3 * c + 1] - verts[3 * a + 1],
-               e22 = verts[3 * c + 2] - verts[3 * a + 2];
-  const double n0 = e11 * e22 - e12 * e21, n1 = e12 * e20 - e10 * e22, n2 = e10 * e21 - e11 * e20;
-  area[p] = 0.5 * sqrt((n0 * n0 + n1 * n1) + n2 * n2);
+  area[p] = prim::tri_area(prim::ld3(verts, tris[3 * t]), prim::ld3(verts, tris[3 * t + 1]),
+                           prim::ld3(verts, tris[3 * t + 2]));
 }
 
 // nb[c]: the 64-blocks of cluster c (starts: its first sorted position).
@@ -252,10 +237,6 @@ __global__ __launch_bounds__(kT) void k_sc_avg(const uint32_t* ustart, int64_t m
   out[3 * o + 2] = p2 / cnt;
 }
 
-bool bad_sizes(int64_t n_v, int64_t n_t) {
-  return n_v < 0 || n_t < 0 || n_v >= (1ll << 31) || 3 * n_t >= (1ll << 32);
-}
-
 }  // namespace mcl
 }  // namespace
 
@@ -283,22 +264,15 @@ int sl_mesh_cluster_triangles(sl_ctx* c, const double* vertices, int64_t n_verti
     if (r) return r;
   }
   prim::StageClock clock(s);
-  const uint64_t nv = static_cast<uint64_t>(n_vertices);
   DBuf<uint32_t> parent, root, flag, pos;
   MTRY(c, parent.alloc(n));
   {
-    DBuf<uint64_t> keys;
-    DBuf<uint32_t> vals;
-    MTRY(c, keys.alloc(n3));
-    MTRY(c, vals.alloc(n3));
-    hipLaunchKernelGGL(k_mc_edges, dim3(blocks(n)), dim3(kT), 0, s, triangles, n, nv, keys.p, vals.p);
-    hipLaunchKernelGGL(prim::k_clu_init, dim3(blocks(n)), dim3(kT), 0, s, n, parent.p);
-    MTRY(c, hipGetLastError());
-    MTRY(c, clock.lap(&tls_ms[0]));
-    r = radix_sort(c, keys.p, vals.p, n3, key_bits(nv * nv - 1), s);  // only the bits the keys have
+    prim::SideTable S;
+    hipLaunchKernelGGL(prim::k_clu_init, dim3(blocks(n)), dim3(kT), 0, s, n, parent.p);  // in stage 0, with the keys
+    r = prim::sort_sides(c, triangles, n, static_cast<uint64_t>(n_vertices), S, nullptr, nullptr, nullptr, clock,
+                         &tls_ms[0], &tls_ms[1], s);
     if (r) return r;
-    MTRY(c, clock.lap(&tls_ms[1]));
-    hipLaunchKernelGGL(k_mc_union, dim3(blocks(n3)), dim3(kT), 0, s, keys.p, vals.p, n3, parent.p);
+    hipLaunchKernelGGL(k_mc_union, dim3(blocks(n3)), dim3(kT), 0, s, S.keys.p, S.vals.p, n3, parent.p);
     MTRY(c, hipGetLastError());
     MTRY(c, clock.lap(&tls_ms[2]));
   }
@@ -359,10 +333,7 @@ int sl_mesh_cluster_triangles(sl_ctx* c, const double* vertices, int64_t n_verti
 }
 
 int sl_mesh_cluster_triangles_stats(double* stage_ms, int capacity) {
-  using namespace mcl;
-  if (capacity < 0 || (capacity && !stage_ms)) return SL_EINVAL;
-  for (int i = 0; i < capacity; ++i) stage_ms[i] = i < 6 ? tls_ms[i] : 0.0;
-  return SL_OK;
+  return prim::copy_stats(mcl::tls_ms, stage_ms, capacity);
 }
 
 int sl_mesh_remove_triangles(sl_ctx* c, const int32_t* triangles, int64_t n_triangles, const uint8_t* mask,

@@ -388,10 +388,7 @@ int sl_mesh_transfer_colors(sl_ctx* c, const double* cloud_xyz, const uint8_t* c
 }
 
 int sl_mesh_transfer_colors_stats(double* stats, int capacity) {
-  using namespace mcol;
-  if (capacity < 0 || (capacity && !stats)) return SL_EINVAL;
-  for (int i = 0; i < capacity; ++i) stats[i] = i < kStats ? tls_stats[i] : 0.0;
-  return SL_OK;
+  return prim::copy_stats(mcol::tls_stats, stats, capacity);
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // libslgpu.so, part 2n -- mesh hole filling, included at the end of slmerge.hip (one translation unit: it uses that
-// file's scratch pool, radix sort, scan and bounds, and slprim.inl's side keys, union-find, input checks and stage
-// clock).  mesh.check can say that a mesh has holes; this closes the ones that are plain loops.  Open3D's tensor
+// file's scratch pool, scan and bounds, and slprim.inl's side table, union-find, input checks and stage clock).
+// mesh.check can say that a mesh has holes; this closes the ones that are plain loops.  Open3D's tensor
 // fill_holes(hole_size) is not in this image: parity with it is UNPINNED, the definitions below are this library's
 // own, and tests/meshfill_oracle.py restates them; the results equal it exactly.  Nothing depends on the order in
 // which sides, loops or vertices are visited, or on the order of the atomics.
@@ -33,11 +33,11 @@
 //             triangle of an n = 3 loop at its label).  A simple loop's vertices each leave once and no two loops
 //             share one, so both orders are flags over the V vertices and a scan: no second sort.
 //
-// Steps.  prim::k_mk_sides and radix_sort as in sl_mesh_check (the same keys).  k_mf_flag marks the runs of one
-// side; scan_flags numbers them; k_mf_sides writes the (from, to) rows, counts the sides that leave and enter every
+// Steps.  prim::sort_sides leaves the sorted side table.  k_mf_flag marks the runs of one side (prim::run_sides);
+// scan_flags numbers them; k_mf_sides writes the (from, to) rows, counts the sides that leave and enter every
 // vertex (integer atomics) and keeps the smallest side at each vertex by atomicMin.  k_mf_union: side j unites with
 // the representative side of each of its two ends (prim::unite: the smallest side of a component is its root).
-// After the kernel boundary k_mf_gather walks to the root with plain loads and accumulates per root: the bad flag,
+// After the kernel boundary k_mf_gather walks to the root (prim::root_of) and accumulates per root: the bad flag,
 // the label (atomicMin), the size, the box as order-preserving integer images of the doubles (atomicMin / atomicMax),
 // the three fixed-point sums and the sum of the vertex indices (of a triangle loop a, b, c the side a->b finds c as
 // that sum - a - b).  k_mf_roots decides per root, k_mf_tflags raises the from-vertices, two scans, k_mf_emit writes.
@@ -67,9 +67,7 @@ __device__ __forceinline__ double unimage(unsigned long long u) {
 
 __global__ __launch_bounds__(kT) void k_mf_flag(const uint64_t* keys, int64_t n3, uint32_t* flag) {
   const int64_t i = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
-  if (i >= n3) return;
-  const uint64_t k = keys[i];
-  flag[i] = ((i == 0 || keys[i - 1] != k) && (i + 1 >= n3 || keys[i + 1] != k)) ? 1u : 0u;
+  if (i < n3) flag[i] = prim::run_sides(keys, i, n3) == 1 ? 1u : 0u;
 }
 
 // The flagged sides as rows j = pos[i]; the per-vertex degrees and smallest side; row j's accumulators start empty.
@@ -117,8 +115,7 @@ __global__ __launch_bounds__(kT) void k_mf_gather(const uint32_t* from, const ui
                                                   double s, uint32_t* root, uint32_t* info, unsigned long long* acc) {
   const int64_t j = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
   if (j >= nb) return;
-  uint32_t r = static_cast<uint32_t>(j);
-  for (uint32_t p = parent[r]; p != r; p = parent[r]) r = p;  // strictly decreasing
+  const uint32_t r = prim::root_of(parent, static_cast<uint32_t>(j));
   root[j] = r;
   const uint32_t a = from[j], b = to[j];
   uint32_t* fi = info + static_cast<int64_t>(kInfo) * r;
@@ -249,23 +246,15 @@ struct Request {  // what the one pass below is asked for (NULL: not written)
 int run(sl_ctx* c, const double* verts, int64_t n_v, const int32_t* tris, int64_t n, const Request& q,
         int64_t* counts, hipStream_t s) {
   const int64_t n3 = 3 * n;
-  const uint64_t nv = static_cast<uint64_t>(n_v);
   prim::StageClock clock(s);
-  DBuf<uint64_t> keys;
-  DBuf<uint32_t> vals, flag, pos;
-  MTRY(c, keys.alloc(n3));
-  MTRY(c, vals.alloc(n3));
-  hipLaunchKernelGGL(prim::k_mk_sides, dim3(blocks(n)), dim3(kT), 0, s, tris, n, nv, keys.p, vals.p,
-                     static_cast<uint32_t*>(nullptr), static_cast<uint32_t*>(nullptr),
-                     static_cast<unsigned long long*>(nullptr));
-  MTRY(c, hipGetLastError());
-  MTRY(c, clock.lap(&tls_ms[0]));
-  int r = radix_sort(c, keys.p, vals.p, n3, key_bits(nv * nv - 1), s);
+  prim::SideTable S;
+  DBuf<uint32_t> flag, pos;
+  int r = prim::sort_sides(c, tris, n, static_cast<uint64_t>(n_v), S, nullptr, nullptr, nullptr, clock, &tls_ms[0],
+                           &tls_ms[1], s);
   if (r) return r;
-  MTRY(c, clock.lap(&tls_ms[1]));
   MTRY(c, flag.alloc(n3));
   MTRY(c, pos.alloc(n3));
-  hipLaunchKernelGGL(k_mf_flag, dim3(blocks(n3)), dim3(kT), 0, s, keys.p, n3, flag.p);
+  hipLaunchKernelGGL(k_mf_flag, dim3(blocks(n3)), dim3(kT), 0, s, S.keys.p, n3, flag.p);
   MTRY(c, hipGetLastError());
   int64_t nb = 0;
   r = scan_flags(c, flag.p, n3, pos.p, &nb, s);
@@ -314,7 +303,7 @@ int run(sl_ctx* c, const double* verts, int64_t n_v, const int32_t* tris, int64_
   MTRY(c, hipMemsetAsync(rep.p, 0xff, sizeof(uint32_t) * n_v, s));
   MTRY(c, hipMemsetAsync(vflags.p, 0, sizeof(uint32_t) * 3 * n_v, s));
   MTRY(c, hipMemsetAsync(cnt.p, 0, sizeof(unsigned long long) * kCounters, s));
-  hipLaunchKernelGGL(k_mf_sides, dim3(blocks(n3)), dim3(kT), 0, s, vals.p, tris, flag.p, pos.p, n3, from.p, to.p,
+  hipLaunchKernelGGL(k_mf_sides, dim3(blocks(n3)), dim3(kT), 0, s, S.vals.p, tris, flag.p, pos.p, n3, from.p, to.p,
                      parent.p, deg_out, deg_in, rep.p, info.p, acc.p);
   MTRY(c, hipGetLastError());
   MTRY(c, clock.lap(&tls_ms[2]));
@@ -435,10 +424,7 @@ int sl_mesh_fill_holes(sl_ctx* c, const double* vertices, int64_t n_vertices, co
 }
 
 int sl_mesh_fill_stats(double* stage_ms, int capacity) {
-  using namespace mfl;
-  if (capacity < 0 || (capacity && !stage_ms)) return SL_EINVAL;
-  for (int i = 0; i < capacity; ++i) stage_ms[i] = i < 6 ? tls_ms[i] : 0.0;
-  return SL_OK;
+  return prim::copy_stats(mfl::tls_ms, stage_ms, capacity);
 }
 
 }  // extern "C"

@@ -2,7 +2,7 @@
 // after the mesh writers (slmeshwrite.inl) and the colour transfer
 // (slmeshcolor.inl), of which it names nothing (one translation unit: it shares
 // slmerge.hip's scratch pool, radix sort, key runs and their starts, and
-// slprim.inl's input checks and stage clock).  Open3D users take the terraces of a scanned mesh out
+// slprim.inl's side table, input checks and stage clock).  Open3D users take the terraces of a scanned mesh out
 // with TriangleMesh::FilterSmoothTaubin; that call, FilterSmoothSimple,
 // FilterSmoothLaplacian and the ComputeAdjacencyList they rest on are restated
 // here, for the vertices alone (normals and colours are not filtered).  Open3D
@@ -10,8 +10,8 @@
 // tests/meshsmooth_oracle.py is the CPU restatement the tests check against,
 // exactly.
 //
-// Input: vertices f64 [V][3], triangles int32 [T][3]; V < 2^31, 6 T < 2^32 (sort
-// values and scans are 32-bit).  k_mc_check reads every index before anything is
+// Input: vertices f64 [V][3], triangles int32 [T][3]; V < 2^31, 6 T < 2^32 (the
+// CSR's entries and scans are 32-bit: prim::bad_csr_sizes).  k_mc_check reads every index before anything is
 // indexed: one outside 0 .. V-1 is SL_EINDEX, never a load.  A non-finite vertex
 // coordinate is SL_EINVAL.
 //
@@ -45,10 +45,9 @@
 //   keeps its position in every step; its neighbours still read it.
 //
 // Adjacency on the device.  The directed pairs (v, w) and (w, v) hold the same
-// information, so only the 3 T undirected sides are sorted.  k_ms_keys writes
-// every side as (key min V + max, value max), keys below 2^62; radix_sort orders
-// them over the bits V V - 1 has; key_runs flags the run heads and scans them and
-// k_seg_starts gathers the unique sides' keys and first positions -- a side's
+// information, so only the 3 T undirected sides are sorted: prim::sort_sides'
+// table, of which the keys alone are read (min V + max holds both ends).
+// key_runs flags the run heads and scans them and k_seg_starts gathers the unique sides' keys and first positions -- a side's
 // run length is its multiplicity, so boundary costs nothing beyond the sort.
 // The unique sides in key order are every vertex's UPPER neighbours (w >= v, v
 // itself when a triangle repeats it), ascending.  The LOWER neighbours are the
@@ -77,7 +76,7 @@ namespace msm {
 
 thread_local double tls_ms[4];  // keys, sort, CSR, iterations of the last call
 
-using prim::require_finite, prim::require_indices;
+using prim::require_finite, prim::require_indices, prim::bad_csr_sizes;
 
 __global__ __launch_bounds__(kT) void k_ms_simple(const double* __restrict__ in, const int64_t* __restrict__ row_start,
                                                   const int32_t* __restrict__ nb, const uint8_t* __restrict__ fixed,
@@ -132,23 +131,6 @@ __global__ __launch_bounds__(kT) void k_ms_laplacian(const double* __restrict__ 
   out[3 * v] = p0;
   out[3 * v + 1] = p1;
   out[3 * v + 2] = p2;
-}
-
-bool bad_sizes(int64_t n_v, int64_t n_t) {
-  return n_v < 0 || n_t < 0 || n_v >= (1ll << 31) || 6 * n_t >= (1ll << 32);
-}
-
-// The three sides of triangle t: key min V + max (the value, max, only rides along: the sort takes pairs).
-__global__ __launch_bounds__(kT) void k_ms_keys(const int32_t* tris, int64_t n_t, uint64_t n_v, uint64_t* keys,
-                                                uint32_t* vals) {
-  const int64_t t = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
-  if (t >= n_t) return;
-  const uint32_t a = static_cast<uint32_t>(tris[3 * t]), b = static_cast<uint32_t>(tris[3 * t + 1]),
-                 c = static_cast<uint32_t>(tris[3 * t + 2]);
-  const uint32_t l0 = min(a, b), h0 = max(a, b), l1 = min(b, c), h1 = max(b, c), l2 = min(c, a), h2 = max(c, a);
-  keys[3 * t] = l0 * n_v + h0, vals[3 * t] = h0;
-  keys[3 * t + 1] = l1 * n_v + h1, vals[3 * t + 1] = h1;
-  keys[3 * t + 2] = l2 * n_v + h2, vals[3 * t + 2] = h2;
 }
 
 // The unique sides transposed: key = the larger end (V for a side {a, a}: it sorts last), value = the smaller.
@@ -211,29 +193,26 @@ struct Sides {
   int64_t n3 = 0, n_e = 0;       // sides, unique sides (the CSR has at most 2 n_e entries)
 };
 
-// keys, both sorts and the runs between them (n_t > 0, indices checked).  The first two stages are timed here;
-// the clock runs on.
+// The side table (its values are not read: the keys hold both ends), the runs and the transposed sort (n_t > 0,
+// indices checked).  The first two stages are timed here, stage 1 being both sorts and the runs between them; the
+// clock runs on.
 int sorted_sides(sl_ctx* c, const int32_t* tris, int64_t n_t, uint64_t nv, Sides& S, prim::StageClock& clock,
                  hipStream_t s) {
-  S.n3 = 3 * n_t;
-  DBuf<uint64_t> keys;
-  DBuf<uint32_t> vals, flag, seg;
-  MTRY(c, keys.alloc(S.n3));
-  MTRY(c, vals.alloc(S.n3));
-  hipLaunchKernelGGL(k_ms_keys, dim3(blocks(n_t)), dim3(kT), 0, s, tris, n_t, nv, keys.p, vals.p);
-  MTRY(c, hipGetLastError());
-  MTRY(c, clock.lap(&tls_ms[0]));
-  int r = radix_sort(c, keys.p, vals.p, S.n3, key_bits(nv * nv - 1), s);  // only the bits the keys have
+  prim::SideTable table;
+  int r = prim::sort_sides(c, tris, n_t, nv, table, nullptr, nullptr, nullptr, clock, &tls_ms[0], nullptr, s);
   if (r) return r;
+  S.n3 = table.n3;
+  const uint64_t* keys = table.keys.p;
+  DBuf<uint32_t> flag, seg;
   MTRY(c, flag.alloc(S.n3));
   MTRY(c, seg.alloc(S.n3));
-  r = key_runs(c, keys.p, S.n3, flag.p, seg.p, &S.n_e, s);
+  r = key_runs(c, keys, S.n3, flag.p, seg.p, &S.n_e, s);
   if (r) return r;
   MTRY(c, S.starts.alloc(S.n_e));
   MTRY(c, S.ukeys.alloc(S.n_e));
   MTRY(c, S.tkeys.alloc(S.n_e));
   MTRY(c, S.tvals.alloc(S.n_e));
-  hipLaunchKernelGGL(k_seg_starts, dim3(blocks(S.n3)), dim3(kT), 0, s, flag.p, seg.p, keys.p, S.n3, S.starts.p,
+  hipLaunchKernelGGL(k_seg_starts, dim3(blocks(S.n3)), dim3(kT), 0, s, flag.p, seg.p, keys, S.n3, S.starts.p,
                      S.ukeys.p);
   hipLaunchKernelGGL(k_ms_tkeys, dim3(blocks(S.n_e)), dim3(kT), 0, s, S.ukeys.p, S.n_e, nv, S.tkeys.p, S.tvals.p);
   MTRY(c, hipGetLastError());
@@ -272,7 +251,7 @@ int sl_mesh_adjacency(sl_ctx* c, const int32_t* triangles, int64_t n_triangles, 
                       void* stream) {
   using namespace msm;
   if (!c) return SL_EINVAL;
-  if (bad_sizes(n_vertices, n_triangles) || !n_neighbours || !row_start ||
+  if (bad_csr_sizes(n_vertices, n_triangles) || !n_neighbours || !row_start ||
       (n_triangles && (!triangles || !neighbours)))
     return slgpu_fail(c, SL_EINVAL, "sl_mesh_adjacency: bad sizes or NULL arguments");
   *n_neighbours = 0;
@@ -303,7 +282,7 @@ int sl_mesh_smooth(sl_ctx* c, const double* vertices, int64_t n_vertices, const 
                    double* out_vertices, void* stream) {
   using namespace msm;
   if (!c) return SL_EINVAL;
-  if (bad_sizes(n_vertices, n_triangles) || (n_vertices && (!vertices || !out_vertices)) ||
+  if (bad_csr_sizes(n_vertices, n_triangles) || (n_vertices && (!vertices || !out_vertices)) ||
       (n_triangles && !triangles))
     return slgpu_fail(c, SL_EINVAL, "sl_mesh_smooth: bad sizes or NULL arguments");
   if (method < 0 || method > 2) return slgpu_fail(c, SL_EINVAL, "sl_mesh_smooth: method must be 0, 1 or 2");
@@ -364,10 +343,7 @@ int sl_mesh_smooth(sl_ctx* c, const double* vertices, int64_t n_vertices, const 
 }
 
 int sl_mesh_smooth_stats(double* stage_ms, int capacity) {
-  using namespace msm;
-  if (capacity < 0 || (capacity && !stage_ms)) return SL_EINVAL;
-  for (int i = 0; i < capacity; ++i) stage_ms[i] = i < 4 ? tls_ms[i] : 0.0;
-  return SL_OK;
+  return prim::copy_stats(msm::tls_ms, stage_ms, capacity);
 }
 
 }  // extern "C"

@@ -452,10 +452,7 @@ int sl_write_mesh_ply_colors_device(sl_ctx* c, const char* path, const double* v
 }
 
 int sl_mesh_write_stats(double* stage_ms, int capacity) {
-  using namespace mwr;
-  if (capacity < 0 || (capacity && !stage_ms)) return SL_EINVAL;
-  for (int i = 0; i < capacity; ++i) stage_ms[i] = i < 3 ? tls_ms[i] : 0.0;
-  return SL_OK;
+  return prim::copy_stats(mwr::tls_ms, stage_ms, capacity);
 }
 
 }  // extern "C"

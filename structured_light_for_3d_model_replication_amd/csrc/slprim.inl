@@ -262,7 +262,12 @@ __global__ __launch_bounds__(kT) void k_sc_heads(const uint32_t* tri, const uint
 }
 
 // ------------------------------------------------------ triangle sides ----
-// (sl_mesh_check's and the boundary loops' one sort: csrc/slmeshcheck.inl's header states the keys)
+// The sorted side table of a mesh: what the components, the adjacency, the checks and the boundary loops all start
+// from.  (a, b, c) has the sides a->b, b->c, c->a; a side's key is min V + max (below 2^62), its value 3 t + k.  The
+// sort is stable and by key alone, so a run holds one undirected edge's sides in ascending 3 t + k.
+// Limits: bad_sizes (V < 2^31 for the keys, 3 T < 2^32 for the values); the adjacency's CSR can hold two entries per
+// side and asks for bad_csr_sizes (6 T < 2^32) instead.
+//
 // dst += the lanes of the wave with p set: one atomic per wave.  Called by all lanes of the wave together.
 __device__ __forceinline__ void wave_add(unsigned long long* dst, bool p) {
   const unsigned long long m = __ballot(p);
@@ -311,9 +316,66 @@ __global__ __launch_bounds__(kT) void k_mk_sides(const int32_t* tris, int64_t n_
   if (n_degenerate) wave_add(n_degenerate, deg);
 }
 
-// the limits of the side keys and of the values 3 t + k
 bool bad_sizes(int64_t n_v, int64_t n_t) {
   return n_v < 0 || n_t < 0 || n_v >= (1ll << 31) || 3 * n_t >= (1ll << 32);
+}
+bool bad_csr_sizes(int64_t n_v, int64_t n_t) { return bad_sizes(n_v, n_t) || 6 * n_t >= (1ll << 32); }
+
+struct SideTable {
+  DBuf<uint64_t> keys;  // [n3] ascending
+  DBuf<uint32_t> vals;  // [n3] 3 t + k
+  int64_t n3 = 0;
+};
+
+// The table of n_t > 0 triangles whose indices were checked; the three optional pointers are k_mk_sides'.  Two laps
+// of the caller's clock: *keys_ms takes what was queued since its last lap and k_mk_sides, *sort_ms the sort
+// (NULL: no second lap, the caller's stage goes on).
+int sort_sides(sl_ctx* c, const int32_t* tris, int64_t n_t, uint64_t n_v, SideTable& S, uint32_t* corner_parent,
+               uint32_t* parity_word, unsigned long long* n_degenerate, StageClock& clock, double* keys_ms,
+               double* sort_ms, hipStream_t s) {
+  S.n3 = 3 * n_t;
+  MTRY(c, S.keys.alloc(S.n3));
+  MTRY(c, S.vals.alloc(S.n3));
+  hipLaunchKernelGGL(k_mk_sides, dim3(blocks(n_t)), dim3(kT), 0, s, tris, n_t, n_v, S.keys.p, S.vals.p, corner_parent,
+                     parity_word, n_degenerate);
+  MTRY(c, hipGetLastError());
+  MTRY(c, clock.lap(keys_ms));
+  const int r = radix_sort(c, S.keys.p, S.vals.p, S.n3, key_bits(n_v * n_v - 1), s);  // only the bits the keys have
+  if (r) return r;
+  if (sort_ms) MTRY(c, clock.lap(sort_ms));
+  return SL_OK;
+}
+
+// 0 when sorted position i < n3 is not the first of its run, else the run's sides: 1, 2, or 3 for three and more.
+// Reads keys[i - 1 .. i + 2] at most.
+__device__ __forceinline__ int run_sides(const uint64_t* keys, int64_t i, int64_t n3) {
+  const uint64_t k = keys[i];
+  if (i > 0 && keys[i - 1] == k) return 0;
+  if (i + 1 >= n3 || keys[i + 1] != k) return 1;
+  return i + 2 < n3 && keys[i + 2] == k ? 3 : 2;
+}
+
+// ------------------------------------------------------------ small pieces ----
+// x's root by plain loads: valid only after the kernel boundary that follows the unions (the header above).
+__device__ __forceinline__ uint32_t root_of(const uint32_t* parent, uint32_t x) {
+  for (uint32_t p = parent[x]; p != x; p = parent[x]) x = p;  // strictly decreasing
+  return x;
+}
+
+// A_t = 0.5 sqrt((n0 n0 + n1 n1) + n2 n2), n = (p1 - p0) x (p2 - p0), f64, uncontracted: the one triangle area.
+__device__ __forceinline__ double tri_area(const D3& p0, const D3& p1, const D3& p2) {
+  const double e10 = p1.x - p0.x, e11 = p1.y - p0.y, e12 = p1.z - p0.z;
+  const double e20 = p2.x - p0.x, e21 = p2.y - p0.y, e22 = p2.z - p0.z;
+  const double n0 = e11 * e22 - e12 * e21, n1 = e12 * e20 - e10 * e22, n2 = e10 * e21 - e11 * e20;
+  return 0.5 * sqrt((n0 * n0 + n1 * n1) + n2 * n2);
+}
+
+// The body of every sl_*_stats(double*, int): the thread's last N figures, zeros behind them.
+template <int N>
+int copy_stats(const double (&tls)[N], double* out, int capacity) {
+  if (capacity < 0 || (capacity && !out)) return SL_EINVAL;
+  for (int i = 0; i < capacity; ++i) out[i] = i < N ? tls[i] : 0.0;
+  return SL_OK;
 }
 
 }  // namespace prim

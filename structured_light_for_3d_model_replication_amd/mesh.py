@@ -379,14 +379,7 @@ def cluster_connected_triangles(vertices, triangles, *, n_vertices=None, area=Tr
     area is summed in ascending triangle index in blocks of 64 (Open3D: in
     breadth-first order), so the last bits can differ.  An index outside
     0 .. V - 1 raises IndexError."""
-    eng = _engine(device)
-    Vx = None if vertices is None else _f64(vertices, eng.device)
-    if Vx is None and n_vertices is None:
-        raise ValueError("vertices or n_vertices is needed")
-    nv = len(Vx) if n_vertices is None else int(n_vertices)
-    if Vx is not None and nv != len(Vx):
-        raise ValueError("n_vertices does not match the vertices")
-    T = _tris(triangles, eng.device)
+    eng, Vx, T, nv = _check_args(vertices, triangles, n_vertices, device)
     t = len(T)
     want = bool(area) and Vx is not None
     labels = torch.empty(max(t, 1), dtype=torch.int32, device=eng.device)
@@ -398,14 +391,23 @@ def cluster_connected_triangles(vertices, triangles, *, n_vertices=None, area=Tr
     return labels[:t], counts[: nc.value], (areas[: nc.value] if want else None)
 
 
+def _stats(device, symbol, n) -> list:
+    """The n doubles that this thread's last call left with the library's ``symbol(double*, int)``."""
+    v = (ctypes.c_double * n)()
+    _lib.check(getattr(_engine(device)._L, symbol)(v, n), None, symbol)
+    return list(v)
+
+
+def _stage_ms(device, symbol, names) -> dict:
+    """``_stats`` under ``names``, in order: host milliseconds per stage."""
+    return dict(zip(names, _stats(device, symbol, len(names))))
+
+
 def cluster_stats(*, device=None) -> dict:
     """Host milliseconds per stage of this thread's last ``cluster_connected_triangles``
     (sl_mesh_cluster_triangles_stats; a measurement aid)."""
-    eng = _engine(device)
-    v = (ctypes.c_double * 6)()
-    _lib.check(eng._L.sl_mesh_cluster_triangles_stats(v, 6), None, "sl_mesh_cluster_triangles_stats")
-    return {"edge_keys_ms": v[0], "sort_ms": v[1], "union_ms": v[2], "flatten_rank_ms": v[3], "counts_ms": v[4],
-            "areas_ms": v[5]}
+    return _stage_ms(device, "sl_mesh_cluster_triangles_stats",
+                     ("edge_keys_ms", "sort_ms", "union_ms", "flatten_rank_ms", "counts_ms", "areas_ms"))
 
 
 def remove_triangles_by_mask(vertices, triangles, mask, *, device=None):
@@ -573,10 +575,7 @@ def filter_smooth_taubin(vertices, triangles, iterations: int = 1, lambda_filter
 def smooth_stats(*, device=None) -> dict:
     """Host milliseconds per stage of this thread's last ``adjacency_list`` or
     ``filter_smooth_*`` (sl_mesh_smooth_stats; a measurement aid)."""
-    eng = _engine(device)
-    v = (ctypes.c_double * 4)()
-    _lib.check(eng._L.sl_mesh_smooth_stats(v, 4), None, "sl_mesh_smooth_stats")
-    return {"keys_ms": v[0], "sort_ms": v[1], "csr_ms": v[2], "iterations_ms": v[3]}
+    return _stage_ms(device, "sl_mesh_smooth_stats", ("keys_ms", "sort_ms", "csr_ms", "iterations_ms"))
 
 
 def _check_args(vertices, triangles, n_vertices, device):
@@ -657,11 +656,8 @@ def check(vertices, triangles, *, n_vertices=None, device=None) -> dict:
 def check_stats(*, device=None) -> dict:
     """Host milliseconds per stage of this thread's last mesh check or measure
     (sl_mesh_check_stats; a measurement aid)."""
-    eng = _engine(device)
-    v = (ctypes.c_double * 7)()
-    _lib.check(eng._L.sl_mesh_check_stats(v, 7), None, "sl_mesh_check_stats")
-    return {"side_keys_ms": v[0], "sort_ms": v[1], "classify_ms": v[2], "corners_ms": v[3], "parity_ms": v[4],
-            "flips_ms": v[5], "measure_ms": v[6]}
+    return _stage_ms(device, "sl_mesh_check_stats",
+                     ("side_keys_ms", "sort_ms", "classify_ms", "corners_ms", "parity_ms", "flips_ms", "measure_ms"))
 
 
 def get_non_manifold_edges(vertices, triangles, allow_boundary_edges: bool = True, *, n_vertices=None, device=None):
@@ -846,11 +842,8 @@ def fill_stats(*, device=None) -> dict:
     """Host milliseconds per stage of this thread's last ``fill_holes`` or
     ``boundary_loops`` call into the library (sl_mesh_fill_stats; a measurement
     aid; both make two calls, the first of which only counts)."""
-    eng = _engine(device)
-    v = (ctypes.c_double * 6)()
-    _lib.check(eng._L.sl_mesh_fill_stats(v, 6), None, "sl_mesh_fill_stats")
-    return {"side_keys_ms": v[0], "sort_ms": v[1], "boundary_ms": v[2], "union_ms": v[3], "loops_ms": v[4],
-            "caps_ms": v[5]}
+    return _stage_ms(device, "sl_mesh_fill_stats",
+                     ("side_keys_ms", "sort_ms", "boundary_ms", "union_ms", "loops_ms", "caps_ms"))
 
 
 def quantile(values, q: float) -> float:
@@ -938,9 +931,7 @@ def ball_pivot_stats(*, device=None) -> dict:
     """Of this thread's last enumeration (sl_ball_pivot_candidates_stats; a
     measurement aid): host milliseconds per stage, the live queries, the candidates and
     the queries that went to the kernel's second tier (a neighbourhood above its first capacity)."""
-    eng = _engine(device)
-    v = (ctypes.c_double * 7)()
-    _lib.check(eng._L.sl_ball_pivot_candidates_stats(v, 7), None, "sl_ball_pivot_candidates_stats")
+    v = _stats(device, "sl_ball_pivot_candidates_stats", 7)
     return {"grid_ms": v[0], "enumerate_ms": v[1], "order_ms": v[2], "live": int(v[3]), "candidates": int(v[4]),
             "second_tier": int(v[6])}
 
@@ -1109,10 +1100,7 @@ def compute_vertex_normals(vertices, triangles, *, device=None) -> torch.Tensor:
 def mesh_write_stats(*, device=None) -> dict:
     """Host milliseconds of this thread's last device write (sl_mesh_write_stats; a
     measurement aid): waiting for packed chunks to land, inside write(), in all."""
-    eng = _engine(device)
-    v = (ctypes.c_double * 3)()
-    _lib.check(eng._L.sl_mesh_write_stats(v, 3), None, "sl_mesh_write_stats")
-    return {"wait_ms": v[0], "write_ms": v[1], "total_ms": v[2]}
+    return _stage_ms(device, "sl_mesh_write_stats", ("wait_ms", "write_ms", "total_ms"))
 
 
 _STL_REC = np.dtype([("normal", "<f4", 3), ("v", "<f4", (3, 3)), ("attr", "<u2")])
@@ -1275,9 +1263,7 @@ def transfer_colors_stats(*, device=None) -> dict:
     """This thread's last ``transfer_colors`` (sl_mesh_transfer_colors_stats; a measurement aid): tiers run,
     vertices filled, host milliseconds in the grid builds and in the query passes, vertices resolved per tier
     (the first 16), tiers that ran the one-wave-per-query kernel."""
-    eng = _engine(device)
-    v = (ctypes.c_double * 21)()
-    _lib.check(eng._L.sl_mesh_transfer_colors_stats(v, 21), None, "sl_mesh_transfer_colors_stats")
+    v = _stats(device, "sl_mesh_transfer_colors_stats", 21)
     tiers = int(v[0])
     return {"tiers": tiers, "filled": int(v[1]), "grid_ms": v[2], "query_ms": v[3],
             "resolved": [int(x) for x in v[4:4 + min(tiers, 16)]], "wave_tiers": int(v[20])}
